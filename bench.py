@@ -2,7 +2,7 @@
 batch 256 pairs per GPU, synthetic inputs, random-init weights of the reference architectures
 (RoBERTa-base + 2 heads, EfficientNet-B0, CLIP ViT-B/32, 2170-row Truth-Vault, FusionJudge).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Both multi-GPU forms run the same ranks: started directly with --gpus N > 1 (no WORLD_SIZE in the
@@ -18,8 +18,15 @@ decode stay outside (the reference's tokenizers / vocab files are not available 
 
 One process per GPU; the batch is sharded (weak scaling: 256 pairs per GPU, no collective on the
 data path -- the barrier and the max-over-ranks time reduction of mmf_amd.benchrun are the only
-RCCL traffic).  Rank 0 prints one JSON line, which also carries the per-config secondary numbers of
-BASELINE configs[1..3] (N = 1 only), the dominant kernel's roofline and the CPU baseline.
+RCCL traffic).  Rank 0 prints one JSON line.
+
+A plain run does what the headline needs and nothing else: engine and inputs, W warm-up steps, K
+timed steps, the line.  --full adds the secondary measurements to the same line: the HBM-resident
+rate, the dominant kernel's roofline, the per-config numbers of BASELINE configs[1..3], the
+per-sample and text+JPEG lines (N = 1 only) and the CPU baseline; each --no-* option leaves one of
+them out of a --full run.  --dump-outputs DIR writes the result arrays of the last timed step (what
+HostPipeline.result returns to a caller) as DIR/<name>.npy, float32; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -80,6 +87,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result arrays of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (HBM-resident rate, per-kernel roofline, BASELINE "
+                         "configs[1..3], per-sample and text+JPEG lines, CPU baseline); the --no-* options "
+                         "below each leave one of them out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of CPU mode (i)")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel event-timed pass")
@@ -319,6 +332,15 @@ def result_line(a, world: int, B: int, dt: float, value: float, data: str, **ext
     return res
 
 
+def dump_outputs(dirname: str, arrays: dict, rank: int) -> None:
+    """--dump-outputs: one float32 .npy per result array (the int32 verdict / rule / top_idx values are
+    small integers, exact in float32).  Rank 0 writes DIR/<name>.npy, rank r > 0 DIR/<name>.rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), v.detach().cpu().numpy().astype(np.float32))
+
+
 def standin_main(a, world: int, rank: int) -> None:
     """--cpu-standin: everything bench.py does around the step -- the rank environment, gloo
     barriers, exactly K timed steps, the max over ranks, the whole-job rate and the JSON line --
@@ -332,8 +354,11 @@ def standin_main(a, world: int, rank: int) -> None:
     B = a.batch
     g = torch.Generator().manual_seed(benchrun.input_seed(rank))
     x, w = torch.randn(B, 768, generator=g), torch.randn(768, 768, generator=g)
-    dt = benchrun.timed_steps(lambda: torch.mm(x, w), a.steps, a.warmup, dist)
+    y = torch.empty(B, 768)
+    dt = benchrun.timed_steps(lambda: torch.mm(x, w, out=y), a.steps, a.warmup, dist)
     value = benchrun.whole_job_rate(world, B, a.steps, dt)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"standin": y}, rank)
     if rank == 0:
         res = result_line(a, world, B, dt, value, "cpu stand-in step (test of the rank launch; not a measurement)",
                           config_extra={"rank_launch": "bench.py" if os.environ.get("MMF_BENCH_PARENT") else
@@ -392,35 +417,40 @@ def main():
     dt = benchrun.timed_steps(lambda: pipe.submit(host), a.steps, a.warmup, dist, sync, tdev)
     value = benchrun.whole_job_rate(world, B, a.steps, dt)
     h2d = sum(v.numel() * v.element_size() for v in host.values())
+    benchrun.progress(f"headline {value:.1f} pairs/s")
+    if a.dump_outputs:
+        if pipe.i == 0:
+            raise SystemExit("--dump-outputs needs at least one step")
+        # what the caller of the last timed submit receives: that slot's pinned host result tensors
+        dump_outputs(a.dump_outputs, pipe.result((pipe.i - 1) % pipe.n), rank)
 
-    benchrun.progress(f"headline {value:.1f} pairs/s; timed region: HBM-resident")
-    # secondary: inputs already resident in HBM
-    out = eng.alloc_outputs(B)
+    hbm_resident = roofline = configs = per_sample = cpu = None
+    if a.full:
+        benchrun.progress("timed region: HBM-resident")
+        # secondary: inputs already resident in HBM
+        out = eng.alloc_outputs(B)
 
-    def step():
-        eng.analyze_batch(t["rid"], t["rm"], t["cid"], t["cm"], t["img"], out=out)
-    dt_hbm = benchrun.timed_steps(step, a.steps, a.warmup, dist, sync, tdev)
-    hbm = benchrun.whole_job_rate(world, B, a.steps, dt_hbm)
-
-    roofline = None
-    if not a.no_profile:
-        benchrun.progress("per-kernel event-timed pass")
-        from mmf_amd.profiling import kernel_roofline
-        roofline = kernel_roofline(eng, step, a.steps)
-    configs = None
-    if world == 1 and not a.no_configs:
-        configs = config_lines(eng, t, a.steps, a.warmup, det)
-    per_sample = None
-    if world == 1 and not a.no_per_sample:
-        per_sample = per_sample_lines()
-    if world == 1 and not a.no_e2e:
-        benchrun.progress("text + JPEG line: analyze_pairs")
-        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-        import e2e_pairs_bench
-        per_sample = dict(per_sample or {}, text_jpeg_pairs=e2e_pairs_bench.bench_line())
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(a.cpu_seconds)
+        def step():
+            eng.analyze_batch(t["rid"], t["rm"], t["cid"], t["cm"], t["img"], out=out)
+        dt_hbm = benchrun.timed_steps(step, a.steps, a.warmup, dist, sync, tdev)
+        hbm = benchrun.whole_job_rate(world, B, a.steps, dt_hbm)
+        hbm_resident = {"value": round(hbm, 2), "unit": "pairs/s", "ms_per_step": round(1000 * dt_hbm / a.steps, 3),
+                        "note": "same step with inputs already in HBM and results left on the device"}
+        if not a.no_profile:
+            benchrun.progress("per-kernel event-timed pass")
+            from mmf_amd.profiling import kernel_roofline
+            roofline = kernel_roofline(eng, step, a.steps)
+        if world == 1 and not a.no_configs:
+            configs = config_lines(eng, t, a.steps, a.warmup, det)
+        if world == 1 and not a.no_per_sample:
+            per_sample = per_sample_lines()
+        if world == 1 and not a.no_e2e:
+            benchrun.progress("text + JPEG line: analyze_pairs")
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+            import e2e_pairs_bench
+            per_sample = dict(per_sample or {}, text_jpeg_pairs=e2e_pairs_bench.bench_line())
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            cpu = cpu_baseline(a.cpu_seconds)
     if rank == 0:
         res = result_line(
             a, world, B, dt, value,
@@ -432,8 +462,7 @@ def main():
                               **({"rehearsal": f"{world} ranks sharing {torch.cuda.device_count()} GPU(s) over gloo "
                                                 "(MMF_BENCH_SHARE_GPU=1): a functional check, not a measurement"}
                                  if share else {})),
-            hbm_resident={"value": round(hbm, 2), "unit": "pairs/s", "ms_per_step": round(1000 * dt_hbm / a.steps, 3),
-                          "note": "same step with inputs already in HBM and results left on the device"},
+            hbm_resident=hbm_resident,
             achieved_tflops_whole_path=round(value * GFLOP_PER_PAIR / 1e3, 1),
             achieved_tflops_whole_path_executed=round(value * GFLOP_EXEC_PER_PAIR / 1e3, 1),
             work_per_pair={"algorithmic_gflop": GFLOP_PER_PAIR, "executed_gflop": GFLOP_EXEC_PER_PAIR,

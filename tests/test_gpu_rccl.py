@@ -12,6 +12,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -28,16 +29,25 @@ def _port():
     return p
 
 
-def test_bench_rccl_timing_leg_world1():
+def test_bench_rccl_timing_leg_world1(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     env = dict(os.environ, MMF_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-profile", "--no-configs", "--no-per-sample", "--no-e2e"]
+           "--no-cpu-baseline", "--no-profile", "--no-configs", "--no-per-sample", "--no-e2e",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=240)
     print(r.stderr[-3000:])
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["value"] > 0
     assert line["config"]["timing_collective"].startswith("rccl"), line["config"]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    # --dump-outputs: the eight result arrays of the last timed step, float32, one row per pair
+    shapes = {"scores": (256, 5), "text_similarity": (256,), "probs": (256, 2), "verdict": (256,),
+              "confidence": (256,), "rule": (256,), "top_sims": (256, 5), "top_idx": (256, 5)}
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{k}.npy" for k in shapes)
+    for k, shape in shapes.items():
+        v = np.load(os.path.join(tmp_path, f"{k}.npy"))
+        assert v.dtype == np.float32 and v.shape == shape and np.isfinite(v).all(), k

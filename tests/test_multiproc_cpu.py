@@ -144,11 +144,20 @@ def test_bench_gpus2_launches_two_ranks():
     assert sum(ln.startswith("{") for ln in p.stdout.splitlines()) == 1  # one JSON line
 
 
-def test_bench_gpus1_is_a_single_process():
-    rc, res, p = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-standin"])
+def test_bench_gpus1_is_a_single_process(tmp_path):
+    rc, res, p = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-standin",
+                             "--dump-outputs", str(tmp_path / "dump")])
     assert rc == 0, p.stderr[-2000:]
     assert res["n_gpus"] == 1 and res["config"]["parallelism"].startswith("replicas x1")
     assert res["config"]["rank_launch"] == "external"  # no child processes were started
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    # --dump-outputs: what the last timed step computed, float32, from the seeded inputs
+    from mmf_amd import benchrun
+    y = np.load(tmp_path / "dump" / "standin.npy")
+    g =torch.Generator().manual_seed(benchrun.input_seed(0))
+    x, w = torch.randn(256, 768, generator=g), torch.randn(768, 768, generator=g)
+    assert y.dtype == np.float32 and y.shape == (256, 768)
+    np.testing.assert_allclose(y, torch.mm(x, w).numpy(), rtol=1e-4, atol=1e-3)
 
 
 def test_bench_failing_rank_fails_the_launch():

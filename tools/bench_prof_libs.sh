@@ -12,5 +12,5 @@ for L in "$@"; do
   i=$((i+1))
   if [ "$L" = default ]; then unset MMF_HIP_LIB; else export MMF_HIP_LIB=$R/$L; fi
   echo "t$i $L" >> $OUT/libs.txt
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -f csv -d $OUT/t$i -o run -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-configs --no-profile > $OUT/t$i.log 2>&1 || exit 1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -f csv -d $OUT/t$i -o run -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-configs --no-profile > $OUT/t$i.log 2>&1 || exit 1
 done
