@@ -1,0 +1,173 @@
+// The EfficientNet-B0 tower's launch sequences (fp16 activations, and the fp32 tower of option
+// effnet_fp32), its block geometry and the workspace sizes that follow from it.
+#include "handle.h"
+
+EffBlock eff_block(int si, int j) {
+  const int* st = kStages[si];
+  EffBlock B{};
+  B.expand = st[0];
+  B.k = st[1];
+  B.stride = j == 0 ? st[2] : 1;
+  B.cin = j == 0 ? st[3] : st[4];
+  B.cout = st[4];
+  B.cexp = B.cin * B.expand;
+  B.csq = B.cin / 4 > 1 ? B.cin / 4 : 1;
+  B.residual = (B.stride == 1 && B.cin == B.cout);
+  return B;
+}
+
+EffSizes eff_sizes() {
+  EffSizes z{(size_t)112 * 112 * 32, 0, 0, 0};
+  int H = 112;
+  for (int si = 0; si < 7; ++si)
+    for (int j = 0; j < kStages[si][5]; ++j) {
+      const EffBlock b = eff_block(si, j);
+      const int Ho = (H - 1) / b.stride + 1;
+      z.exp = std::max(z.exp, (size_t)H * H * b.cexp);
+      z.dw = std::max(z.dw, (size_t)Ho * Ho * b.cexp);
+      z.io = std::max(z.io, (size_t)Ho * Ho * b.cout);
+      z.pool = std::max(z.pool, (size_t)dwconv_nchunks(H, H, b.cexp, b.stride) * b.cexp);
+      H = Ho;
+    }
+  z.exp = std::max(z.exp, (size_t)7 * 7 * 1280);
+  return z;
+}
+
+namespace {
+
+// The EfficientNet activation workspaces hold max_batch images at the largest per-image size of each
+// buffer; a batch chunk that starts at image b0 works in the disjoint slice b0 * (per-image max) on,
+// so chunks of one batch can run concurrently on different streams (mmf_effnet_forward).
+template <typename T>
+struct EffWs {
+  T *e_a, *e_b, *e_exp, *e_dw;  // T = f16_t: the fp16 tower; float: the fp32 tower's (Workspace e32_*)
+  float *e_pool, *e_scale;
+};
+template <typename T>
+EffWs<T> eff_ws(const Workspace& w, T* a, T* b, T* exp, T* dw, int b0) {
+  const EffSizes es = eff_sizes();
+  const size_t i = (size_t)b0;
+  return EffWs<T>{a + i * es.io, b + i * es.io, exp + i * es.exp, dw + i * es.dw, w.e_pool + i * es.pool,
+                  w.e_scale + i * 1280};
+}
+
+// The fp32 tower (option effnet_fp32): same network, same folded weights (fp32 copies of the 1x1
+// convs), activations fp32 throughout -- no fusion, one launch per layer.
+int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score,
+                 int score_stride, hipStream_t s, int img0) {
+  if (h->ws.e32_cap_b < img0 + B) return fail(MMF_EINVAL, "effnet_fp32: fp32 tower workspaces not reserved");
+  const EffWs<float> w = eff_ws(h->ws, h->ws.e32_a, h->ws.e32_b, h->ws.e32_exp, h->ws.e32_dw, img0);
+  float* cur = w.e_a;
+  float* nxt = w.e_b;
+  {
+    ProfScope ps(h, s, PK_STEM, 2.0 * B * 112 * 112 * 32 * 27, (double)B * (224 * 224 * 3 + 112 * 112 * 32 * 4));
+    HIPCHK(launch_effnet_stem32(img, xf32, h->e_stem_w, h->e_stem_b, cur, B, s));
+  }
+  int H = 112, W = 112;
+  for (const EffBlock& b : h->e_blocks) {
+    const int Ho = (H - 1) / b.stride + 1, Wo = (W - 1) / b.stride + 1;
+    const float* src = cur;
+    if (b.expand != 1) {
+      ProfScope ps(h, s, PK_PW32, 2.0 * B * H * W * b.cin * b.cexp, 4.0 * B * H * W * (b.cin + b.cexp));
+      HIPCHK(launch_pw32(cur, b.e.w32, b.e.b, nullptr, 1, nullptr, w.e_exp, B * H * W, b.cexp, b.cin, 3 /* SiLU */, s,
+                             h->opt.pw32_mfma));
+      src = w.e_exp;
+    }
+    {
+      ProfScope ps(h, s, PK_DW, 2.0 * B * Ho * Wo * b.cexp * b.k * b.k, 4.0 * B * b.cexp * ((double)H * W + Ho * Wo));
+      HIPCHK(launch_dw32(src, b.wd_t, b.bd, w.e_dw, B, H, W, b.cexp, b.k, b.stride, s));
+    }
+    {
+      ProfScope ps(h, s, PK_SE, 4.0 * B * b.cexp * b.csq, 4.0 * B * b.cexp * ((double)Ho * Wo + 2));
+      // as many pool chunks as the fp16 tower uses for this layer (fits e_pool by construction)
+      const int nch = std::min(dwconv_nchunks(H, W, b.cexp, b.stride), Ho * Wo);
+      HIPCHK(launch_sum32(w.e_dw, B, Ho * Wo, b.cexp, nch, w.e_pool, s));
+      HIPCHK(launch_se(w.e_pool, nch, 1.0f / (float)(Ho * Wo), b.w1, b.b1, b.w2, b.b2, w.e_scale, B, b.cexp, b.csq, s,
+                       true));
+    }
+    {
+      ProfScope ps(h, s, PK_PW32, 2.0 * B * Ho * Wo * b.cexp * b.cout,
+                   4.0 * B * Ho * Wo * (b.cexp + b.cout * (b.residual ? 2 : 1)));
+      HIPCHK(launch_pw32(w.e_dw, b.p.w32, b.p.b, w.e_scale, Ho * Wo, b.residual ? cur : nullptr, nxt, B * Ho * Wo,
+                         b.cout, b.cexp, 0, s, h->opt.pw32_mfma));
+    }
+    std::swap(cur, nxt);
+    H = Ho;
+    W = Wo;
+  }
+  {
+    ProfScope ps(h, s, PK_PW32, 2.0 * B * H * W * 320 * 1280, 4.0 * B * H * W * (320 + 1280));
+    HIPCHK(launch_pw32(cur, h->e_head.w32, h->e_head.b, nullptr, 1, nullptr, w.e_exp, B * H * W, 1280, 320, 3, s,
+                       h->opt.pw32_mfma));
+  }
+  ProfScope ps(h, s, PK_GAP, (double)B * H * W * 1280 + 4.0 * B * 1280, (double)B * H * W * 1280 * 4);
+  HIPCHK(launch_gap32(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
+  return 0;
+}
+
+}  // namespace
+
+int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score, int score_stride,
+               hipStream_t s, int img0) {
+  if (h->opt.effnet_fp32) return run_effnet32(h, img, xf32, B, logits, score, score_stride, s, img0);
+  const EffWs<f16_t> w = eff_ws(h->ws, h->ws.e_a, h->ws.e_b, h->ws.e_exp, h->ws.e_dw, img0);
+  f16_t* cur = w.e_a;
+  f16_t* nxt = w.e_b;
+  // option fuse_stem = 0: separate stem launch + stage-1 depthwise (A/B and parity tests)
+  const EffBlock& b0 = h->e_blocks.front();
+  const bool fuse_stem = h->opt.fuse_stem && b0.expand == 1 && b0.cexp == 32 && b0.k == 3 && b0.stride == 1;
+  if (!fuse_stem) {
+    ProfScope ps(h, s, PK_STEM, 2.0 * B * 112 * 112 * 32 * 27, (double)B * (224 * 224 * 3 + 112 * 112 * 32 * 2));
+    if (xf32) HIPCHK(launch_effnet_stem_f32(xf32, h->e_stem_w, h->e_stem_b, cur, B, s));
+    else HIPCHK(launch_effnet_stem(img, h->e_stem_w, h->e_stem_b, cur, B, s));
+  }
+  int H = 112, W = 112;
+  for (const EffBlock& b : h->e_blocks) {
+    const f16_t* src = cur;
+    int nch = 0;
+    const int Ho = (H - 1) / b.stride + 1, Wo = (W - 1) / b.stride + 1;
+    // option fuse_expand = 0: separate expand launch (A/B)
+    const bool fuse = b.expand != 1 && h->opt.fuse_expand && expand_dw_applicable(b.cin, b.cexp, b.k);
+    if (&b == &b0 && fuse_stem) {
+      // stem output recomputed per 18x18 halo tile: 1.27x the stem MACs, image patch read once
+      ProfScope ps(h, s, PK_DW, 2.0 * B * 112 * 112 * 32 * (9 + 27 * 1.27),
+                   (double)B * (224 * 224 * 3 * 1.34 + 112 * 112 * 32 * 2));
+      HIPCHK(launch_effnet_stem_dw(img, xf32, h->e_stem_w, h->e_stem_b, b.wd, b.bd, w.e_dw, w.e_pool, B, &nch, s));
+    } else if (fuse) {
+      ProfScope ps(h, s, PK_DW, 2.0 * B * Ho * Wo * b.cexp * b.k * b.k + 2.0 * B * H * W * b.cin * b.cexp,
+                   (double)B * 2 * ((double)H * W * b.cin * (b.cexp / 48) + (double)Ho * Wo * b.cexp));
+      HIPCHK(launch_expand_dw(cur, b.cin, b.e.w, b.e.b, b.wd, b.bd, w.e_dw, w.e_pool, B, H, W, b.cexp, b.k, b.stride,
+                              &nch, s));
+    } else if (b.expand != 1) {
+      GemmArgs g = gemm_args(cur, b.cin, b.e, B * H * W);
+      g.act = 3;  // SiLU
+      g.c16 = w.e_exp;
+      CHK(gemm(h, g, s));
+      src = w.e_exp;
+    }
+    if (!fuse && !(&b == &b0 && fuse_stem)) {
+      ProfScope ps(h, s, PK_DW, 2.0 * B * Ho * Wo * b.cexp * b.k * b.k,
+                   (double)B * b.cexp * 2 * ((double)H * W + (double)Ho * Wo));
+      HIPCHK(launch_dwconv(src, b.wd, b.bd, w.e_dw, w.e_pool, B, H, W, b.cexp, b.k, b.stride, &nch, s,
+                            1 | (h->opt.dw_cw32 ? 8 : 0)));
+    }
+    ProfScope ps(h, s, PK_SE, 4.0 * B * b.cexp * b.csq, (double)B * b.cexp * 4 * (nch + 1));
+    HIPCHK(launch_se(w.e_pool, nch, 1.0f / (float)(Ho * Wo), b.w1, b.b1, b.w2, b.b2, w.e_scale, B, b.cexp, b.csq, s));
+    GemmArgs g = gemm_args(w.e_dw, b.cexp, b.p, B * Ho * Wo);
+    g.ascale = w.e_scale;
+    g.rows_per_batch = Ho * Wo;
+    if (b.residual) g.res16 = cur;
+    g.c16 = nxt;
+    CHK(gemm(h, g, s));
+    std::swap(cur, nxt);
+    H = Ho;
+    W = Wo;
+  }
+  GemmArgs g = gemm_args(cur, 320, h->e_head, B * H * W);
+  g.act = 3;
+  g.c16 = w.e_exp;
+  CHK(gemm(h, g, s));
+  ProfScope ps(h, s, PK_GAP, (double)B * H * W * 1280 + 4.0 * B * 1280, (double)B * H * W * 1280 * 2);
+  HIPCHK(launch_gap_classifier(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
+  return 0;
+}

@@ -27,7 +27,7 @@ class Engine:
     """MI355X replica of the MisinfoForensics models on one device."""
 
     EFFNET_PRECISIONS = ("auto", "fp16", "fp32")
-    # RoBERTa stream / operand precision -> option text_hilo (capi.cpp run_text / run_text_precise):
+    # RoBERTa stream / operand precision -> option text_hilo (csrc/text_host.cpp run_text / run_text_precise):
     # "auto" = the LayerNorm-bound layout (-1: fp16 or split stream) unless the load-time calibration
     # selects "precise"; the others pin the mode ("fp16" / "split" also skip packing the precise weights)
     TEXT_PRECISIONS = {"auto": -1, "fp16": 0, "split": 1, "precise": 2}
