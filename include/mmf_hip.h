@@ -294,6 +294,47 @@ int mmf_gemm_f16_split(const void* A, int lda, const void* W, int ldw, const flo
 int mmf_attention_f16(const void* qkv, const int32_t* mask, void* out, int B, int L, int H, int causal,
                        void* stream);
 
+/* Low-level ops exported for unit tests of the fp16 EfficientNet kernels (tests/test_gpu_effnet_kernels.py).
+ * No handle; every pointer is a device pointer; work is enqueued on `stream`.  Activations are fp16
+ * NHWC ([B][H][W][C]), weights and biases fp32 with BatchNorm already folded.  A shape a kernel does
+ * not support is MMF_EINVAL, decided on the host before anything is launched.
+ *
+ * Depthwise k x k convolution (k 3 or 5, stride 1 or 2, zero padding (k - 1) / 2) + SiLU:
+ *   in [B][H][W][C] -> out [B][Ho][Wo][C], Ho = (H - 1) / stride + 1; w [C][k*k], bias [C];
+ *   pool_part [B][nchunks][C] fp32 = per output tile (row-major tiles of edge T, the largest divisor of
+ *   Ho up to 16 / 8 for stride 1 / 2) the sum of the unrounded outputs; nchunks = mmf_dwconv_nchunks
+ *   (host arithmetic only; MMF_EINVAL on a bad shape).  flags bit 0: compile-time tile geometries where
+ *   one exists; bit 3: 32-channel groups where C % 32 == 0.  C % 48 == 0 or C % 32 == 0; B <= 65535;
+ *   H * W * C < 2^30. */
+int mmf_dwconv_nchunks(int H, int W, int C, int stride);
+int mmf_dwconv_f16(const void* in, const float* w, const float* bias, void* out, float* pool_part, int B, int H, int W,
+                   int C, int k, int stride, int flags, void* stream);
+/* The same behind a fused 1x1 expand + SiLU: x fp16 [B][H][W][cin], we fp16 [C][cin], be fp32 [C]; the
+ * expanded activation (rounded to fp16, as the separate GEMM stores it) feeds the depthwise conv above.
+ * cin % 8 == 0, C % 48 == 0, cin <= 64 (k = 5) or <= 96 (k = 3), (k, stride, ceil(cin / 32)) one of
+ * (3,2,1) (3,1,1) (5,2,1) (5,1,2) (3,2,2) (3,1,3), input tile edge (T - 1) stride + k <= 19.
+ * ct 1: compile-time geometries where one exists. */
+int mmf_expand_dw_f16(const void* x, int cin, const void* we, const float* be, const float* w, const float* bias,
+                      void* out, float* pool_part, int B, int H, int W, int C, int k, int stride, int ct, void* stream);
+/* Squeeze-excitation: pooled[c] = inv_hw * sum_j pool_part[b][j][c]; s1 = SiLU(w1 pooled + b1), w1 [Csq][C];
+ * scale [B][C] = sigmoid(w2t^T s1 + b2), w2t [Csq][C] (fc2's weight transposed).  precise 1: the SiLU by
+ * expf and a division (the fp32 tower's).  C <= 1280, Csq <= 64. */
+int mmf_se_f32(const float* pool_part, int nchunks, float inv_hw, const float* w1, const float* b1, const float* w2t,
+               const float* b2, float* scale, int B, int C, int Csq, int precise, void* stream);
+/* Stem: ToTensor + Normalize (ImageNet) -> conv 3x3 stride 2 pad 1, 3 -> 32 + SiLU -> out fp16 [B][112][112][32].
+ * Exactly one of img_u8 (uint8 [B][224][224][3]) and x_f32_nchw (normalised fp32 [B][3][224][224]) is
+ * non-NULL; w [32][3][3][3], bias [32]. */
+int mmf_effnet_stem_f16(const uint8_t* img_u8, const float* x_f32_nchw, const float* w, const float* bias, void* out,
+                        int B, void* stream);
+/* The stem fused into the stage-1 depthwise conv (3x3, stride 1, 32 channels): ws / bs the stem's, wd [32][9] /
+ * bd [32] the depthwise conv's; out fp16 [B][112][112][32], pool_part [B][49][32] (16 x 16 tiles). */
+int mmf_effnet_stem_dw_f16(const uint8_t* img_u8, const float* x_f32_nchw, const float* ws, const float* bs,
+                           const float* wd, const float* bd, void* out, float* pool_part, int B, void* stream);
+/* Global average pool + Linear(C, 2) + softmax: x fp16 [B][HW][C], w [2][C], b [2] -> logits [B][2] and / or
+ * score[b * score_stride] = softmax(logits[b])[1] (either may be NULL, not both).  C % 8 == 0. */
+int mmf_gap_classifier_f16(const void* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
+                           int score_stride, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

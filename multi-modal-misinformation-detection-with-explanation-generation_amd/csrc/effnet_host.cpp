@@ -171,3 +171,94 @@ int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, floa
   HIPCHK(launch_gap_classifier(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
   return 0;
 }
+
+// ---- test-only entry points: the fp16 tower's kernels on raw device operands (include/mmf_hip.h;
+// tests/test_gpu_effnet_kernels.py).  Every shape check runs on the host before anything is launched.
+namespace {
+
+// a launcher's hipErrorInvalidValue is its "unsupported shape" answer; anything else is a HIP failure
+int test_launch_rc(hipError_t e, const char* what) {
+  if (e == hipSuccess) return 0;
+  if (e == hipErrorInvalidValue) return fail(MMF_EINVAL, "%s: unsupported shape", what);
+  return fail(MMF_EIO, "%s: %s", what, hipGetErrorString(e));
+}
+
+// what the depthwise launchers' geometry arithmetic and 32-bit byte offsets assume
+bool dw_shape_ok(int B, int H, int W, int C, int k, int stride) {
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || C <= 0) return false;
+  if ((k != 3 && k != 5) || (stride != 1 && stride != 2)) return false;
+  return (double)H * W * C * 2.0 < 2147483648.0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmf_dwconv_nchunks(int H, int W, int C, int stride) {
+  if (H <= 0 || W <= 0 || C <= 0 || (stride != 1 && stride != 2)) return fail(MMF_EINVAL, "dwconv_nchunks: bad shape");
+  return dwconv_nchunks(H, W, C, stride);
+}
+
+int mmf_dwconv_f16(const void* in, const float* w, const float* bias, void* out, float* pool_part, int B, int H, int W,
+                   int C, int k, int stride, int flags, void* stream) {
+  if (!in || !w || !bias || !out || !pool_part) return fail(MMF_EINVAL, "null argument");
+  if (!dw_shape_ok(B, H, W, C, k, stride))
+    return fail(MMF_EINVAL, "dwconv: unsupported shape (B=%d H=%d W=%d C=%d k=%d stride=%d)", B, H, W, C, k, stride);
+  int nch = 0;
+  return test_launch_rc(launch_dwconv((const f16_t*)in, w, bias, (f16_t*)out, pool_part, B, H, W, C, k, stride, &nch,
+                                      (hipStream_t)stream, flags),
+                        "dwconv");
+}
+
+int mmf_expand_dw_f16(const void* x, int cin, const void* we, const float* be, const float* w, const float* bias,
+                      void* out, float* pool_part, int B, int H, int W, int C, int k, int stride, int ct, void* stream) {
+  if (!x || !we || !be || !w || !bias || !out || !pool_part) return fail(MMF_EINVAL, "null argument");
+  if (!dw_shape_ok(B, H, W, C, k, stride) || cin <= 0 || !expand_dw_applicable(cin, C, k))
+    return fail(MMF_EINVAL, "expand_dw: not applicable (cin=%d C=%d k=%d stride=%d B=%d H=%d W=%d)", cin, C, k, stride,
+                B, H, W);
+  int nch = 0;
+  return test_launch_rc(launch_expand_dw((const f16_t*)x, cin, (const f16_t*)we, be, w, bias, (f16_t*)out, pool_part,
+                                         B, H, W, C, k, stride, &nch, (hipStream_t)stream, ct),
+                        "expand_dw");
+}
+
+int mmf_se_f32(const float* pool_part, int nchunks, float inv_hw, const float* w1, const float* b1, const float* w2t,
+               const float* b2, float* scale, int B, int C, int Csq, int precise, void* stream) {
+  if (!pool_part || !w1 || !b1 || !w2t || !b2 || !scale) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || nchunks <= 0 || C <= 0 || Csq <= 0)
+    return fail(MMF_EINVAL, "se: bad shape (B=%d nchunks=%d C=%d Csq=%d)", B, nchunks, C, Csq);
+  return test_launch_rc(
+      launch_se(pool_part, nchunks, inv_hw, w1, b1, w2t, b2, scale, B, C, Csq, (hipStream_t)stream, precise != 0), "se");
+}
+
+int mmf_effnet_stem_f16(const uint8_t* img_u8, const float* x_f32_nchw, const float* w, const float* bias, void* out,
+                        int B, void* stream) {
+  if (!w || !bias || !out) return fail(MMF_EINVAL, "null argument");
+  if (!img_u8 == !x_f32_nchw) return fail(MMF_EINVAL, "stem: exactly one of img_u8 / x_f32_nchw");
+  if (B <= 0) return fail(MMF_EINVAL, "stem: bad batch %d", B);
+  const hipError_t e = x_f32_nchw ? launch_effnet_stem_f32(x_f32_nchw, w, bias, (f16_t*)out, B, (hipStream_t)stream)
+                                  : launch_effnet_stem(img_u8, w, bias, (f16_t*)out, B, (hipStream_t)stream);
+  return test_launch_rc(e, "stem");
+}
+
+int mmf_effnet_stem_dw_f16(const uint8_t* img_u8, const float* x_f32_nchw, const float* ws, const float* bs,
+                           const float* wd, const float* bd, void* out, float* pool_part, int B, void* stream) {
+  if (!ws || !bs || !wd || !bd || !out || !pool_part) return fail(MMF_EINVAL, "null argument");
+  if (!img_u8 == !x_f32_nchw) return fail(MMF_EINVAL, "stem_dw: exactly one of img_u8 / x_f32_nchw");
+  if (B <= 0 || B > 65535) return fail(MMF_EINVAL, "stem_dw: bad batch %d", B);
+  int nch = 0;
+  return test_launch_rc(
+      launch_effnet_stem_dw(img_u8, x_f32_nchw, ws, bs, wd, bd, (f16_t*)out, pool_part, B, &nch, (hipStream_t)stream),
+      "stem_dw");
+}
+
+int mmf_gap_classifier_f16(const void* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
+                           int score_stride, int B, void* stream) {
+  if (!x || !w || !b || (!logits && !score)) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || HW <= 0 || C <= 0) return fail(MMF_EINVAL, "gap_classifier: bad shape (B=%d HW=%d C=%d)", B, HW, C);
+  return test_launch_rc(
+      launch_gap_classifier((const f16_t*)x, HW, C, w, b, logits, score, score_stride, B, (hipStream_t)stream),
+      "gap_classifier");
+}
+
+}  // extern "C"

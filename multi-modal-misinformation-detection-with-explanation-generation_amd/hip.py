@@ -57,6 +57,13 @@ SIGNATURES = {
     "mmf_gemm_f16_ex": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "mmf_gemm_f16_split": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mmf_attention_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_dwconv_nchunks": (_I, [_I, _I, _I, _I]),
+    "mmf_dwconv_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mmf_expand_dw_f16": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mmf_se_f32": (_I, [_P, _I, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_effnet_stem_f16": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "mmf_effnet_stem_dw_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mmf_gap_classifier_f16": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
 }
 
 _lib = None
