@@ -214,6 +214,41 @@ int mmf_analyze_batch(mmf_handle* h, const int32_t* rob_ids, const int32_t* rob_
                       int32_t* verdict, float* confidence, int32_t* rule, float* top_sims, int32_t* top_idx,
                       void* stream);
 
+/* analyze() for a batch of B posts where each has a text, an image or both
+ * (misinfo_forensics.py:790-899), in one launch sequence; each tower runs only on the rows that
+ * have its modality.
+ *
+ * mmf_mixed_plan: host-only, no handle, no device call.  modality uint8 [B] is a bit field per row
+ * (1 = text, 2 = image, 3 = both) -> row_map int32 [B][3] = the row's position in the text list, the
+ * image list and the both list (each list holds its rows in ascending batch order), -1 where the row
+ * is not in the list; counts int32 [3] = {nT, nI, nC}, the lists' lengths.  MMF_EINVAL on NULL, B <= 0
+ * or an entry that is 0 or > 3 (the reference's "Provide at least one of ..." error; nothing is
+ * written past that row).
+ *
+ * mmf_analyze_mixed: inputs are COMPACTED device arrays: rob_ids / rob_mask int32 [nT, Lr] (the text
+ * rows), img_effnet / img_clip uint8 [nI, 224, 224, 3] (the image rows; img_clip may be NULL =
+ * img_effnet), clip_ids / clip_mask int32 [nC, Lc] (the rows with both).  A list whose count is 0 may
+ * be NULL and its tower is not launched.  row_map is a DEVICE int32 [B][3] (mmf_mixed_plan's, copied
+ * by the caller: no H2D copy happens inside the call); nT, nI, nC are passed by value and must
+ * satisfy nT + nI - nC == B, nC <= nT, nC <= nI.  A map entry outside [0, n) of its list is treated
+ * as absent, so no map makes a kernel read out of bounds.  Only the components the batch uses must
+ * be loaded (text rows: RoBERTa + heads; image rows: EfficientNet + CLIP vision; both rows: + CLIP
+ * text + fusion layer), else MMF_EINVAL.  B <= the reserved batch, lengths as mmf_analyze_batch.
+ * Outputs: as mmf_analyze_batch, [B, ...] in batch order.  Per row:
+ *   text only: ai, misinfo from RoBERTa; deepfake, clip_similarity, vault_discrepancy, text_sim and
+ *              top_sims 0, top_idx -1; fake = clamp(misinfo, 0, 1)
+ *   image only: deepfake from EfficientNet, vault top-5 / discrepancy of the ViT embedding; ai,
+ *              misinfo, clip_similarity, text_sim 0; fake = clamp(max(deepfake, vault_discrepancy), 0, 1)
+ *   both:      every output bit-identical to mmf_analyze_batch on that row
+ *   single-modality rows: probs2 = (1 - fake, fake), verdict = fake > 0.5, confidence = verdict ?
+ *              fake : 1 - fake; rule = the same cascade over the row's five scores in all cases. */
+int mmf_mixed_plan(const uint8_t* modality, int B, int32_t* row_map, int32_t* counts);
+int mmf_analyze_mixed(mmf_handle* h, const int32_t* row_map, int B, int nT, int nI, int nC,
+                      const int32_t* rob_ids, const int32_t* rob_mask, int Lr, const int32_t* clip_ids,
+                      const int32_t* clip_mask, int Lc, const uint8_t* img_effnet, const uint8_t* img_clip,
+                      float* scores5, float* text_sim, float* probs2, int32_t* verdict, float* confidence,
+                      int32_t* rule, float* top_sims, int32_t* top_idx, void* stream);
+
 /* Per-kernel timing for roofline accounting: while profiling is on, every kernel launch of the
  * forward calls is bracketed by two hipEvents on its stream.  mmf_profile_end synchronises and
  * aggregates per kernel kind (arrays of >= 16 entries): launch counts, summed device ms, summed

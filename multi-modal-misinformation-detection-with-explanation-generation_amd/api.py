@@ -26,7 +26,7 @@ import torch.nn as nn
 import xxhash
 
 from . import explain, io_utils, weights as W
-from .engine import Engine, SCORE_KEYS
+from .engine import Engine, NO_INPUT_ERROR, SCORE_KEYS
 from .hip import MMFError
 
 _DEFAULT_CLIP_DIR = r"C:\Users\Lenovo\OneDrive\Desktop\hack\models\clip-vit-b32"
@@ -711,10 +711,7 @@ class MisinfoForensics:
         if not chunks:
             return []
 
-        use_jpeg = self.device_jpeg
-        if use_jpeg and self._jpeg is None:
-            from . import jpeg
-            self._jpeg = jpeg.JpegStager()
+        self._ensure_jpeg_stager()
 
         def host_stage(a, b):
             # (tokenising on a third thread while the images decode measured a tie for one chunk and
@@ -722,17 +719,7 @@ class MisinfoForensics:
             rob = io_utils.tokenize_roberta_batch(self.roberta_tokenizer, texts[a:b])
             rid, rm = io_utils.pad_ids(rob, W.ROBERTA["pad_id"])
             cid, cm = self._clip_ids(list(texts[a:b]))
-            # JPEG bytes / files: entropy-decoded here, reconstructed on the device; everything else
-            # decoded by Pillow (pixels); the resampling to both towers' windows runs on the device
-            st = None
-            rest = list(range(b - a))
-            if use_jpeg:
-                from . import jpeg
-                st = self._jpeg.stage([jpeg.read_bytes(x) for x in images[a:b]])
-                done = set(st.index)
-                rest = [i for i in rest if i not in done]
-            rgb = io_utils.decode_rgb([images[a + i] for i in rest]) if rest else []
-            return rid, rm, cid, cm, (b - a, st, rest, rgb)
+            return rid, rm, cid, cm, self._stage_images(images[a:b])
 
         res: List[Dict] = []
 
@@ -749,9 +736,35 @@ class MisinfoForensics:
                 out = self.batch_to_host(self.analyze_batch(rid, rm, cid, cm, eff, clp))
             res.extend(self.batch_to_dicts(out))
 
+        self._run_chunks(chunks, host_stage, device_part)
+        return res
+
+    def _ensure_jpeg_stager(self) -> None:
+        if self.device_jpeg and self._jpeg is None:
+            from . import jpeg
+            self._jpeg = jpeg.JpegStager()
+
+    def _stage_images(self, images) -> Tuple:
+        """Host stage of a chunk's images, the argument tuple of _windows.  JPEG bytes / files:
+        entropy-decoded here, reconstructed on the device; everything else decoded by Pillow
+        (pixels); the resampling to both towers' windows runs on the device."""
+        st = None
+        rest = list(range(len(images)))
+        if self.device_jpeg:
+            from . import jpeg
+            st = self._jpeg.stage([jpeg.read_bytes(x) for x in images])
+            done = set(st.index)
+            rest = [i for i in rest if i not in done]
+        rgb = io_utils.decode_rgb([images[i] for i in rest]) if rest else []
+        return len(images), st, rest, rgb
+
+    @staticmethod
+    def _run_chunks(chunks, host_stage, device_part) -> None:
+        """device_part(host_stage(a, b)) per chunk (a, b), in order; the host stage of chunk i + 1 on a
+        helper thread while chunk i is on the device."""
         if len(chunks) == 1:  # nothing to overlap: no staging thread (analyze(): one pair per call)
             device_part(host_stage(*chunks[0]))
-            return res
+            return
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=1) as ex:
             fut = ex.submit(host_stage, *chunks[0])
@@ -760,6 +773,59 @@ class MisinfoForensics:
                 if k + 1 < len(chunks):
                     fut = ex.submit(host_stage, *chunks[k + 1])
                 device_part(staged)
+
+    def analyze_many(self, texts: List[Optional[str]], images: List) -> List[Dict]:
+        """Batched analyze() for a feed of posts where each has a text, an image or both: texts[i] /
+        images[i] that is None or empty is absent (the reference's truthiness test,
+        misinfo_forensics.py:793-811).  One analyze_mixed launch sequence per `max_batch` posts -- each
+        tower runs only on the rows that have its modality -- then the reference's result dict per
+        post, in order (rows without an image report no vault matches).  Chunking, the staging thread
+        and the device JPEG decode / resampling of the images are analyze_pairs'.  A post with neither
+        raises the reference's ValueError before anything is tokenised, decoded or launched."""
+        if len(texts) != len(images):
+            raise ValueError(f"{len(texts)} texts vs {len(images)} images")
+
+        def present(x) -> bool:
+            if x is None:
+                return False
+            return len(x) > 0 if isinstance(x, (str, bytes, bytearray)) else True
+        mod = np.array([int(present(t)) | int(present(i)) << 1 for t, i in zip(texts, images)], np.uint8)
+        if (mod == 0).any():
+            raise ValueError(NO_INPUT_ERROR)
+        cap = self.engine.max_batch
+        chunks = [(i, min(i + cap, len(texts))) for i in range(0, len(texts), cap)]
+        if not chunks:
+            return []
+        self._ensure_jpeg_stager()
+
+        def host_stage(a, b):
+            m = mod[a:b]
+            tx = [texts[a + i] for i in np.flatnonzero(m & 1)]    # the text rows, in batch order
+            both = [texts[a + i] for i in np.flatnonzero(m == 3)]  # the rows with both
+            im = [images[a + i] for i in np.flatnonzero(m & 2)]    # the image rows
+            rid = rm = cid = cm = None
+            if tx:
+                rob = io_utils.tokenize_roberta_batch(self.roberta_tokenizer, tx)
+                rid, rm = io_utils.pad_ids(rob, W.ROBERTA["pad_id"])
+            if both:
+                cid, cm = self._clip_ids(both)
+            return m, rid, rm, cid, cm, (self._stage_images(im) if im else None)
+
+        res: List[Dict] = []
+
+        def device_part(staged):
+            m, rid, rm, cid, cm, rgb = staged
+            if rid is not None:
+                self._fit_text(rid.shape[1])
+            eff, clp = self._windows(*rgb) if rgb is not None else (None, None)
+            out = self.batch_to_host(self.analyze_mixed(m, rid, rm, cid, cm, eff, clp))
+            # the run-time precision traps of analyze_pairs on the scores read back (an absent signal's
+            # 0 is finite)
+            if self.engine.scores_overflow(out["scores"]):
+                out = self.batch_to_host(self.analyze_mixed(m, rid, rm, cid, cm, eff, clp))
+            res.extend(self.batch_to_dicts(out, modality=m))
+
+        self._run_chunks(chunks, host_stage, device_part)
         return res
 
     def _windows(self, n: int, st, rest: List[int], rgb: List[np.ndarray]):
@@ -811,19 +877,31 @@ class MisinfoForensics:
         self.detector.sync()
         return self.engine.analyze_batch(rob_ids, rob_mask, clip_ids, clip_mask, images_u8, clip_images_u8, out=out)
 
+    def analyze_mixed(self, modality, rob_ids, rob_mask, clip_ids, clip_mask, images_u8, clip_images_u8=None,
+                      out: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+        """Tensor entry point for posts with a text, an image or both, next to analyze_batch:
+        modality [B] (1 text, 2 image, 3 both) and COMPACT inputs -- ids of the text rows, uint8
+        [nI,224,224,3] windows of the image rows, CLIP ids of the rows with both (a list without rows
+        may be None) -> analyze_batch's dict of [B, ...] device tensors in batch order."""
+        self.detector.sync()
+        return self.engine.analyze_mixed(modality, rob_ids, rob_mask, clip_ids, clip_mask, images_u8, clip_images_u8,
+                                         out=out)
+
     @staticmethod
     def batch_to_host(out: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
         return {k: v.cpu().numpy() for k, v in out.items()}
 
-    def batch_to_dicts(self, out: Dict) -> List[Dict]:
+    def batch_to_dicts(self, out: Dict, modality=None) -> List[Dict]:
         """The reference's result dicts from analyze_batch's outputs (device tensors or their
-        batch_to_host copies)."""
+        batch_to_host copies); modality (analyze_mixed's, per row): a row without an image reports no
+        vault matches."""
         o = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
         res = []
         for b in range(o["scores"].shape[0]):
             s = o["scores"][b]
+            searched = self.vault_loaded and (modality is None or int(modality[b]) & 2)
             vault = (self._vault_dict(o["top_sims"][b], o["top_idx"][b], float(s[4]), float(o["text_similarity"][b]))
-                     if self.vault_loaded else {"vault_discrepancy": 0.0, "matches": [], "text_similarity": 0.0})
+                     if searched else {"vault_discrepancy": 0.0, "matches": [], "text_similarity": 0.0})
             all_scores = {"ai_score": float(s[0]), "misinfo_score": float(s[1]), "deepfake_score": float(s[2]),
                           "clip_similarity": float(s[3]), "vault_discrepancy": float(s[4]),
                           "text_similarity": float(vault.get("text_similarity", 0.0)),

@@ -122,6 +122,122 @@ int analyze_tail(mmf_handle* h, int B, float* scores5, float* text_sim, float* p
   return 0;
 }
 
+// The towers of one step: mmf_analyze_batch runs every tower on all B rows, mmf_analyze_mixed each on
+// the rows that have its modality (a tower with no rows is not launched).  The ViT writes w.v_emb and
+// the CLIP text tower w.t_emb; the text and EfficientNet scores go where the caller says.
+struct TowerJobs {
+  const int32_t *rob_ids, *rob_mask;  // [nT][Lr]
+  int nT, Lr;
+  float* text_scores;  // (ai, misinfo) at text_scores[r * text_stride + {0, 1}]
+  int text_stride;
+  const int32_t *clip_ids, *clip_mask;  // [nC][Lc]
+  int nC, Lc;
+  const uint8_t *img_eff, *img_clip;  // [nI][224][224][3]
+  int nI;
+  float* eff_scores;  // deepfake at eff_scores[r * eff_stride]
+  int eff_stride;
+};
+
+// fork from stream s, run the towers side by side, join back into s.  B = the step's batch rows (it
+// picks the enqueue form: host threads for B <= mt_enqueue, the event chain above it)
+int run_towers(mmf_handle* h, const TowerJobs& j, int B, hipStream_t s) {
+  Workspace& w = h->ws;
+  // the per-kernel profiling pass runs the towers sequentially so event intervals are clean
+  const int concurrent = h->opt.concurrent && !h->prof;
+  if (concurrent) CHK(ensure_towers(h));
+  // fork: the four towers only share read-only inputs and write disjoint workspaces/outputs
+  hipStream_t st_text = s, st_eff = s, st_ctxt = s;
+  if (concurrent) {
+    HIPCHK(hipEventRecord(h->fork_ev, s));
+    for (int i = 0; i < 3; ++i) HIPCHK(hipStreamWaitEvent(h->tower[i], h->fork_ev, 0));
+    st_text = h->tower[0];
+    st_eff = h->tower[1];
+    st_ctxt = h->tower[2];
+  }
+  // diag_skip (diagnostic only, never set by the API or bench.py): towers left out to measure each
+  // tower's marginal cost in the concurrent step (bit 1 text, 2 EfficientNet, 4 CLIP text, 8 ViT)
+  const int skip = h->opt.diag_skip;
+  const bool on_text = !(skip & 1) && j.nT > 0, on_ctxt = !(skip & 4) && j.nC > 0;
+  const bool on_eff = !(skip & 2) && j.nI > 0, on_vit = !(skip & 8) && j.nI > 0;
+  const int32_t *rob_ids = j.rob_ids, *rob_mask = j.rob_mask, *clip_ids = j.clip_ids, *clip_mask = j.clip_mask;
+  const uint8_t *img_eff = j.img_eff, *img_clip = j.img_clip;
+  const int nT = j.nT, Lr = j.Lr, nC = j.nC, Lc = j.Lc, nI = j.nI, text_stride = j.text_stride, eff_stride = j.eff_stride;
+  float *text_scores = j.text_scores, *eff_scores = j.eff_scores;
+  if (concurrent && h->opt.mt_enqueue > 0 && B <= h->opt.mt_enqueue) {
+    // small batches: three host threads enqueue the text, CLIP-text and EfficientNet towers while
+    // this thread enqueues the ViT, so every chain starts at once (each stream keeps its own order)
+    EnqueuePool& pool = ensure_pool(h);
+    float* t_emb = w.t_emb;
+    const bool on[3] = {on_text, on_ctxt, on_eff};
+    if (on[0]) pool.submit(0, [=] { return run_text(h, rob_ids, rob_mask, nT, Lr, nullptr, nullptr, text_scores, text_stride, st_text); });
+    if (on[1]) pool.submit(1, [=] { return run_clip_text(h, clip_ids, clip_mask, nC, Lc, t_emb, st_ctxt); });
+    if (on[2]) pool.submit(2, [=] { return run_effnet(h, img_eff, nullptr, nI, nullptr, eff_scores, eff_stride, st_eff, 0); });
+    const int rc = on_vit ? run_clip_image(h, img_clip, nI, w.v_emb, s) : 0;
+    int wrc = 0;
+    std::string werr;  // the first failing worker's message (wait() writes it only on failure)
+    for (int i = 0; i < 3; ++i) {
+      if (!on[i]) continue;
+      const int r = pool.wait(i, wrc ? nullptr : &werr);
+      if (r && !wrc) wrc = r;
+    }
+    CHK(rc);
+    if (wrc) return fail(wrc, "%s", werr.c_str());
+  } else {
+    // option after_text: the chosen towers' streams wait for the RoBERTa tower (its persistent GEMMs
+    // then own every CU instead of sharing them with the other towers' launches)
+    // (releasing them before RoBERTa's last layer or two, and EfficientNet chained behind a CLIP tower or
+    // split over two streams, measured slower: DESIGN.md §1 round 5)
+    const int after = concurrent && on_text ? h->opt.after_text : 0;
+    if (on_text) CHK(run_text(h, rob_ids, rob_mask, nT, Lr, nullptr, nullptr, text_scores, text_stride, st_text, after ? h->text_ev : nullptr));
+    if (after) {
+      if (after & 2) HIPCHK(hipStreamWaitEvent(st_eff, h->text_ev, 0));
+      if (after & 4) HIPCHK(hipStreamWaitEvent(st_ctxt, h->text_ev, 0));
+      if (after & 8) HIPCHK(hipStreamWaitEvent(s, h->text_ev, 0));
+    }
+    if (on_ctxt) CHK(run_clip_text(h, clip_ids, clip_mask, nC, Lc, w.t_emb, st_ctxt));
+    if (on_eff) CHK(run_effnet(h, img_eff, nullptr, nI, nullptr, eff_scores, eff_stride, st_eff));
+    if (on_vit) CHK(run_clip_image(h, img_clip, nI, w.v_emb, s));
+  }
+  if (concurrent) {
+    for (int i = 0; i < 3; ++i) {
+      HIPCHK(hipEventRecord(h->join_ev[i], h->tower[i]));
+      HIPCHK(hipStreamWaitEvent(s, h->join_ev[i], 0));
+    }
+  }
+  return 0;
+}
+
+// after the towers of mmf_analyze_mixed joined: vault top-5 of the nI image rows into the compact
+// workspaces, then the finish kernel (gather, cosines, scatter, fusion or single-modality verdict)
+int mixed_tail(mmf_handle* h, const int32_t* row_map, int B, int nT, int nI, int nC, float* scores5, float* text_sim,
+               float* probs2, int32_t* verdict, float* conf, int32_t* rule, float* top_sims, int32_t* top_idx,
+               hipStream_t s) {
+  Workspace& w = h->ws;
+  const bool vault = nI > 0 && (h->ready & RDY_VAULT);
+  if (vault) {
+    ProfScope ps(h, s, PK_VAULT, 2.0 * nI * h->vault_n * 512, (double)h->vault_n * 512 * 4 + (double)nI * h->vault_n * 8);
+    HIPCHK(launch_vault_sims(w.v_emb, h->vault, w.s_sims, nI, h->vault_n, 512, s, h->opt.vault_ref));
+    HIPCHK(launch_vault_topk(w.s_sims, nI, h->vault_n, 5, 0.85f, w.m_sims, w.m_idx, w.m_disc, 1, nullptr, nullptr, 512,
+                             nullptr, s, h->opt.vault_ref));
+  }
+  MixedFinishArgs a{};
+  a.row_map = row_map;
+  a.B = B; a.nT = nT; a.nI = nI; a.nC = nC;
+  a.text2 = w.m_text;
+  a.deepfake = w.m_eff;
+  a.v_emb = w.v_emb;
+  a.t_emb = w.t_emb;
+  if (vault) { a.c_sims = w.m_sims; a.c_idx = w.m_idx; a.c_disc = w.m_disc; a.title = h->vault_title; }
+  a.thresh = 0.85f;
+  if (nC > 0) { a.w0 = h->f_w0; a.b0 = h->f_b0; a.w3 = h->f_w3; a.b3 = h->f_b3; a.w5 = h->f_w5; a.b5 = h->f_b5; }
+  a.scores5 = scores5; a.text_sim = text_sim; a.probs = probs2;
+  a.verdict = verdict; a.conf = conf; a.rule = rule;
+  a.top_sims = top_sims; a.top_idx = top_idx;
+  ProfScope ps(h, s, PK_FUSION, 2.0 * nC * (5 * 64 + 64 * 32 + 32 * 2 + 2 * 512), (double)B * (3 + 5 + 2 + 3 + 10) * 4);
+  HIPCHK(launch_mixed_finish(a, s));
+  return 0;
+}
+
 
 // Workspaces of the precision modes, allocated while the mode is selected and freed when it is left
 // (mmf_reserve, mmf_set_option, mmf_finalize) -- never from inside a launch sequence, which worker
@@ -321,6 +437,11 @@ int mmf_reserve(mmf_handle* h, int B, int Lr, int Lc) {
   CHK(A(&w.e_dw, nb * es.dw));
   CHK(A(&w.e_pool, nb * es.pool));
   CHK(A(&w.e_scale, nb * 1280));
+  CHK(A(&w.m_text, nb * 2));
+  CHK(A(&w.m_eff, nb));
+  CHK(A(&w.m_sims, nb * 5));
+  CHK(A(&w.m_idx, nb * 5));
+  CHK(A(&w.m_disc, nb));
   h->cap_b = B;
   h->cap_lr = Lr;
   h->cap_lc = Lc;
@@ -507,64 +628,42 @@ int mmf_analyze_batch(mmf_handle* h, const int32_t* rob_ids, const int32_t* rob_
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   if (!img_clip) img_clip = img_eff;
-  Workspace& w = h->ws;
-  // the per-kernel profiling pass runs the towers sequentially so event intervals are clean
-  const int concurrent = h->opt.concurrent && !h->prof;
-  if (concurrent) CHK(ensure_towers(h));
-  // fork: the four towers only share read-only inputs and write disjoint workspaces/outputs
-  hipStream_t st_text = s, st_eff = s, st_ctxt = s;
-  if (concurrent) {
-    HIPCHK(hipEventRecord(h->fork_ev, s));
-    for (int i = 0; i < 3; ++i) HIPCHK(hipStreamWaitEvent(h->tower[i], h->fork_ev, 0));
-    st_text = h->tower[0];
-    st_eff = h->tower[1];
-    st_ctxt = h->tower[2];
-  }
-  // diag_skip (diagnostic only, never set by the API or bench.py): towers left out to measure each
-  // tower's marginal cost in the concurrent step (bit 1 text, 2 EfficientNet, 4 CLIP text, 8 ViT)
-  const int skip = h->opt.diag_skip;
-  if (concurrent && h->opt.mt_enqueue > 0 && B <= h->opt.mt_enqueue) {
-    // small batches: three host threads enqueue the text, CLIP-text and EfficientNet towers while
-    // this thread enqueues the ViT, so every chain starts at once (each stream keeps its own order)
-    EnqueuePool& pool = ensure_pool(h);
-    float* t_emb = w.t_emb;
-    const bool on[3] = {!(skip & 1), !(skip & 4), !(skip & 2)};
-    if (on[0]) pool.submit(0, [=] { return run_text(h, rob_ids, rob_mask, B, Lr, nullptr, nullptr, scores5, 5, st_text); });
-    if (on[1]) pool.submit(1, [=] { return run_clip_text(h, clip_ids, clip_mask, B, Lc, t_emb, st_ctxt); });
-    if (on[2]) pool.submit(2, [=] { return run_effnet(h, img_eff, nullptr, B, nullptr, scores5 + 2, 5, st_eff, 0); });
-    const int rc = (skip & 8) ? 0 : run_clip_image(h, img_clip, B, w.v_emb, s);
-    int wrc = 0;
-    std::string werr;  // the first failing worker's message (wait() writes it only on failure)
-    for (int i = 0; i < 3; ++i) {
-      if (!on[i]) continue;
-      const int r = pool.wait(i, wrc ? nullptr : &werr);
-      if (r && !wrc) wrc = r;
-    }
-    CHK(rc);
-    if (wrc) return fail(wrc, "%s", werr.c_str());
-  } else {
-    // option after_text: the chosen towers' streams wait for the RoBERTa tower (its persistent GEMMs
-    // then own every CU instead of sharing them with the other towers' launches)
-    // (releasing them before RoBERTa's last layer or two, and EfficientNet chained behind a CLIP tower or
-    // split over two streams, measured slower: DESIGN.md §1 round 5)
-    const int after = concurrent && !(skip & 1) ? h->opt.after_text : 0;
-    if (!(skip & 1)) CHK(run_text(h, rob_ids, rob_mask, B, Lr, nullptr, nullptr, scores5, 5, st_text, after ? h->text_ev : nullptr));
-    if (after) {
-      if (after & 2) HIPCHK(hipStreamWaitEvent(st_eff, h->text_ev, 0));
-      if (after & 4) HIPCHK(hipStreamWaitEvent(st_ctxt, h->text_ev, 0));
-      if (after & 8) HIPCHK(hipStreamWaitEvent(s, h->text_ev, 0));
-    }
-    if (!(skip & 4)) CHK(run_clip_text(h, clip_ids, clip_mask, B, Lc, w.t_emb, st_ctxt));
-    if (!(skip & 2)) CHK(run_effnet(h, img_eff, nullptr, B, nullptr, scores5 + 2, 5, st_eff));
-    if (!(skip & 8)) CHK(run_clip_image(h, img_clip, B, w.v_emb, s));
-  }
-  if (concurrent) {
-    for (int i = 0; i < 3; ++i) {
-      HIPCHK(hipEventRecord(h->join_ev[i], h->tower[i]));
-      HIPCHK(hipStreamWaitEvent(s, h->join_ev[i], 0));
-    }
-  }
+  TowerJobs j{};
+  j.rob_ids = rob_ids; j.rob_mask = rob_mask; j.nT = B; j.Lr = Lr; j.text_scores = scores5; j.text_stride = 5;
+  j.clip_ids = clip_ids; j.clip_mask = clip_mask; j.nC = B; j.Lc = Lc;
+  j.img_eff = img_eff; j.img_clip = img_clip; j.nI = B; j.eff_scores = scores5 + 2; j.eff_stride = 5;
+  CHK(run_towers(h, j, B, s));
   return analyze_tail(h, B, scores5, text_sim, probs2, verdict, conf, rule, top_sims, top_idx, s);
+}
+
+int mmf_analyze_mixed(mmf_handle* h, const int32_t* row_map, int B, int nT, int nI, int nC, const int32_t* rob_ids,
+                      const int32_t* rob_mask, int Lr, const int32_t* clip_ids, const int32_t* clip_mask, int Lc,
+                      const uint8_t* img_eff, const uint8_t* img_clip, float* scores5, float* text_sim, float* probs2,
+                      int32_t* verdict, float* conf, int32_t* rule, float* top_sims, int32_t* top_idx, void* stream) {
+  if (!h || !row_map || !scores5 || !probs2) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || nT < 0 || nI < 0 || nC < 0 || nC > nT || nC > nI || nT + nI - nC != B)
+    return fail(MMF_EINVAL, "counts nT=%d nI=%d nC=%d do not describe a batch of B=%d rows with a text, an image or both "
+                            "(nT + nI - nC == B, nC <= nT, nC <= nI)", nT, nI, nC, B);
+  if ((nT && (!rob_ids || !rob_mask)) || (nI && !img_eff) || (nC && (!clip_ids || !clip_mask)))
+    return fail(MMF_EINVAL, "null input of a list with rows (nT=%d nI=%d nC=%d)", nT, nI, nC);
+  // only the components this batch uses must be loaded
+  const int need = (nT ? RDY_TEXT : 0) | (nI ? RDY_EFFNET | RDY_VISION : 0) | (nC ? RDY_CTEXT | RDY_FUSION : 0);
+  if ((h->ready & need) != need)
+    return fail(MMF_EINVAL, "models of this batch not loaded (needs mask %d, ready mask %d)", need, h->ready);
+  if (!nT) Lr = 1;
+  if (!nC) Lc = 1;
+  if (Lr <= 0 || Lc <= 0 || Lr > 512 || Lc > 77) return fail(MMF_EINVAL, "lengths Lr=%d (1..512) Lc=%d (1..77)", Lr, Lc);
+  CHK(check_cap(h, B, Lr, Lc));
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!img_clip) img_clip = img_eff;
+  Workspace& w = h->ws;
+  TowerJobs j{};
+  j.rob_ids = rob_ids; j.rob_mask = rob_mask; j.nT = nT; j.Lr = Lr; j.text_scores = w.m_text; j.text_stride = 2;
+  j.clip_ids = clip_ids; j.clip_mask = clip_mask; j.nC = nC; j.Lc = Lc;
+  j.img_eff = img_eff; j.img_clip = img_clip; j.nI = nI; j.eff_scores = w.m_eff; j.eff_stride = 1;
+  CHK(run_towers(h, j, B, s));
+  return mixed_tail(h, row_map, B, nT, nI, nC, scores5, text_sim, probs2, verdict, conf, rule, top_sims, top_idx, s);
 }
 
 int mmf_profile_begin(mmf_handle* h) {

@@ -1,7 +1,8 @@
 // Internal to libmmf_hip.so (not installed): the handle behind include/mmf_hip.h, its error, allocation
 // and profiling plumbing, and the launch wrappers the towers share.  The host side is one file per
 // seam: weights_host.cpp packs the weights, text_host.cpp / clip_host.cpp / effnet_host.cpp hold the
-// towers' launch sequences, resize_host.cpp the Pillow resize planner, capi.cpp the extern "C" surface.
+// towers' launch sequences, resize_host.cpp the Pillow resize planner, capi.cpp the extern "C" surface (mixed_plan.cpp: its one
+// host-only function that needs neither the handle nor HIP).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,6 +119,10 @@ struct Workspace {
   // vault
   float* s_sims = nullptr;
   int s_cap_n = 0;
+  // mmf_analyze_mixed: the towers' compact results (text scores [nT][2], deepfake [nI], vault top-5
+  // and discrepancy of the nI image rows) that its finish kernel gathers into batch order
+  float *m_text = nullptr, *m_eff = nullptr, *m_sims = nullptr, *m_disc = nullptr;
+  int32_t* m_idx = nullptr;
 };
 constexpr int kLnP = 8;  // lazy-LN partials per row a GEMM accepts (gemm.hip kLnPMax)
 

@@ -145,6 +145,29 @@ hipError_t launch_text_heads(const float* x, int row_stride, const float* w1a, c
 hipError_t launch_fusion(const float* x5, const float* w0, const float* b0, const float* w3, const float* b3,
                          const float* w5, const float* b5, float* probs, int32_t* verdict, float* conf,
                          int32_t* rule, int B, hipStream_t s);
+// mmf_analyze_mixed's last kernel: per batch row, the row's compact tower results gathered through
+// row_map [B][3] (position of the row in the text / image / both lists; anything outside [0, n) is
+// absent), the CLIP cosine and the caption-title cosine of the "both" rows, the vault outputs scattered
+// (or the no-image convention: 0, 0, -1), the FusionJudge MLP for the "both" rows and the reference's
+// single-modality verdict for the rest (misinfo_forensics.py:879-899), the rule cascade for all
+struct MixedFinishArgs {
+  const int32_t* row_map;
+  int B, nT, nI, nC;
+  const float* text2;    // [nT][2] ai, misinfo
+  const float* deepfake; // [nI]
+  const float* v_emb;    // [nI][512] unit image embeddings
+  const float* t_emb;    // [nC][512] unit caption embeddings
+  const float* c_sims;   // [nI][5] vault top-5 (null: no vault set)
+  const int32_t* c_idx;  // [nI][5]
+  const float* c_disc;   // [nI]
+  const float* title;    // [N][512] unit title embeddings or null
+  float thresh;
+  const float *w0, *b0, *w3, *b3, *w5, *b5;  // fusion layer (read only when nC > 0)
+  float *scores5, *text_sim, *probs;         // [B][5], [B] (nullable), [B][2]
+  int32_t* verdict; float* conf; int32_t* rule;  // [B] each, nullable
+  float* top_sims; int32_t* top_idx;             // [B][5] each, nullable
+};
+hipError_t launch_mixed_finish(const MixedFinishArgs& a, hipStream_t s);
 // cosine of unit rows: out[b*ostride] = dot(a[b], c[b])
 hipError_t launch_rowdot(const float* a, const float* c, float* out, int ostride, int B, int C, hipStream_t s);
 // vault: S[B][N] = Q[B][D] . V[N][D]^T (fp32)

@@ -89,82 +89,176 @@ __global__ __launch_bounds__(1024) void text_heads_kernel(const float* x, int ro
 // fully exposed: a thread per row walked ~2.4k dependent FMAs, ~17 us).  Lane o computes hidden
 // unit o of Linear(5,64), lanes < 32 the units of Linear(64,32) from the wave's LDS row, lane 0
 // the two logits; every dot product keeps the ascending-index fmaf order of the scalar form.
+// The pieces below are shared by fusion_kernel / rowdot_kernel / vault_topk_kernel and by
+// mixed_finish_kernel (mmf_analyze_mixed), so a row's bits do not depend on which of them computed it.
+//
+// The block's LDS image of the fusion layer (4 waves = 4 rows per block)
+struct FusionLds {
+  float sw0[64 * 5], sb0[64], sw3[32 * 65], sb3[32], sw5[64], sb5[2];
+  float hs[4][64], h2[4][32];
+};
+
+// stage the weights (all 256 threads; the caller's __syncthreads() follows)
+MMF_DEV void fusion_stage(FusionLds& L, const float* w0, const float* b0, const float* w3, const float* b3,
+                          const float* w5, const float* b5, int tid) {
+  for (int i = tid; i < 320; i += 256) L.sw0[i] = w0[i];
+  for (int i = tid; i < 2048; i += 256) L.sw3[(i >> 6) * 65 + (i & 63)] = w3[i];  // padded rows: no bank conflicts
+  if (tid < 64) { L.sb0[tid] = b0[tid]; L.sw5[tid] = w5[tid]; }
+  if (tid < 32) L.sb3[tid] = b3[tid];
+  if (tid < 2) L.sb5[tid] = b5[tid];
+}
+
+// the MLP of the wave's row x[5] from the staged weights -> softmax (p0, p1), valid on every lane.
+// Called by all 256 threads of the block after the barrier that follows fusion_stage.
+MMF_DEV void fusion_mlp(FusionLds& L, const float* x, int wave, int lane, float* p0, float* p1) {
+  {
+    float a = L.sb0[lane];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) a = fmaf(L.sw0[lane * 5 + i], x[i], a);
+    L.hs[wave][lane] = fmaxf(a, 0.f);
+  }
+  __syncthreads();
+  if (lane < 32) {
+    float a = L.sb3[lane];
+#pragma unroll 16
+    for (int i = 0; i < 64; ++i) a = fmaf(L.sw3[lane * 65 + i], L.hs[wave][i], a);
+    L.h2[wave][lane] = fmaxf(a, 0.f);
+  }
+  __syncthreads();
+  float l0 = L.sb5[0], l1 = L.sb5[1];
+  for (int o = 0; o < 32; ++o) {
+    l0 = fmaf(L.sw5[o], L.h2[wave][o], l0);
+    l1 = fmaf(L.sw5[32 + o], L.h2[wave][o], l1);
+  }
+  const float m = fmaxf(l0, l1);
+  const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+  *p0 = e0 / (e0 + e1);
+  *p1 = e1 / (e0 + e1);
+}
+
+// _generate_fallback_explanation's cascade (misinfo_forensics.py:742-765) over (ai, misinfo, deepfake,
+// clip_similarity, vault_discrepancy)
+MMF_DEV int explanation_rule(const float* x) {
+  int rr = 5;
+  if (x[4] > 0.7f) rr = 0;
+  else if (x[2] > 0.7f) rr = 1;
+  else if (x[0] > 0.7f) rr = 2;
+  else if (x[1] > 0.7f) rr = 3;
+  else if (x[3] < 0.3f) rr = 4;
+  return rr;
+}
+
+// one row's (probs, verdict, confidence, rule) from the probabilities (p0 real, p1 fake) -- lane 0 only
+MMF_DEV void write_verdict(int row, float p0, float p1, const float* x, float* probs, int32_t* verdict, float* conf,
+                           int32_t* rule) {
+  probs[(size_t)row * 2] = p0;
+  probs[(size_t)row * 2 + 1] = p1;
+  const int v = p1 > 0.5f ? 1 : 0;
+  if (verdict) verdict[row] = v;
+  if (conf) conf[row] = v ? p1 : p0;
+  if (rule) rule[row] = explanation_rule(x);
+}
+
+// dot product of two rows of C floats by one wave (result on every lane): 8 columns per lane in flight,
+// then the ascending-i fmaf chain per lane and the wave sum
+MMF_DEV float wave_rowdot(const float* a, const float* c, int C, int lane) {
+  float s = 0.f;
+  for (int i0 = lane; i0 < C; i0 += 512) {
+    float ta[8], tc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = i0 + 64 * u;
+      ta[u] = i < C ? a[i] : 0.f;
+      tc[u] = i < C ? c[i] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (i0 + 64 * u < C) s = fmaf(ta[u], tc[u], s);
+  }
+  return wave_sum(s);
+}
+
 __global__ __launch_bounds__(256) void fusion_kernel(const float* x5, const float* w0, const float* b0,
                                                      const float* w3, const float* b3, const float* w5,
                                                      const float* b5, float* probs, int32_t* verdict, float* conf,
                                                      int32_t* rule, int B) {
-  __shared__ float sw0[64 * 5], sb0[64], sw3[32 * 65], sb3[32], sw5[64], sb5[2];
-  __shared__ float hs[4][64], h2[4][32];
+  __shared__ FusionLds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = blockIdx.x * 4 + wave;
   const bool live = row < B;
   float x[5];  // (issued before the weight staging: one load latency for both)
 #pragma unroll
   for (int i = 0; i < 5; ++i) x[i] = live ? x5[(size_t)row * 5 + i] : 0.f;
-  for (int i = tid; i < 320; i += 256) sw0[i] = w0[i];
-  for (int i = tid; i < 2048; i += 256) sw3[(i >> 6) * 65 + (i & 63)] = w3[i];  // padded rows: no bank conflicts
-  if (tid < 64) { sb0[tid] = b0[tid]; sw5[tid] = w5[tid]; }
-  if (tid < 32) sb3[tid] = b3[tid];
-  if (tid < 2) sb5[tid] = b5[tid];
+  fusion_stage(L, w0, b0, w3, b3, w5, b5, tid);
   __syncthreads();
-  {
-    float a = sb0[lane];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) a = fmaf(sw0[lane * 5 + i], x[i], a);
-    hs[wave][lane] = fmaxf(a, 0.f);
-  }
-  __syncthreads();
-  if (lane < 32) {
-    float a = sb3[lane];
-#pragma unroll 16
-    for (int i = 0; i < 64; ++i) a = fmaf(sw3[lane * 65 + i], hs[wave][i], a);
-    h2[wave][lane] = fmaxf(a, 0.f);
-  }
-  __syncthreads();
+  float p0, p1;
+  fusion_mlp(L, x, wave, lane, &p0, &p1);
   if (!live || lane != 0) return;
-  float l0 = sb5[0], l1 = sb5[1];
-  for (int o = 0; o < 32; ++o) {
-    l0 = fmaf(sw5[o], h2[wave][o], l0);
-    l1 = fmaf(sw5[32 + o], h2[wave][o], l1);
-  }
-  const float m = fmaxf(l0, l1);
-  const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-  const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-  probs[(size_t)row * 2] = p0;
-  probs[(size_t)row * 2 + 1] = p1;
-  const int v = p1 > 0.5f ? 1 : 0;
-  if (verdict) verdict[row] = v;
-  if (conf) conf[row] = v ? p1 : p0;
-  if (rule) {
-    int rr = 5;
-    if (x[4] > 0.7f) rr = 0;
-    else if (x[2] > 0.7f) rr = 1;
-    else if (x[0] > 0.7f) rr = 2;
-    else if (x[1] > 0.7f) rr = 3;
-    else if (x[3] < 0.3f) rr = 4;
-    rule[row] = rr;
-  }
+  write_verdict(row, p0, p1, x, probs, verdict, conf, rule);
 }
 
 __global__ __launch_bounds__(256) void rowdot_kernel(const float* a, const float* c, float* out, int ostride, int B,
                                                      int C) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= B) return;
-  float s = 0.f;
-  for (int i0 = lane; i0 < C; i0 += 512) {  // 8 columns per lane in flight, then the ascending-i chain
-    float ta[8], tc[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + 64 * u;
-      ta[u] = i < C ? a[(size_t)row * C + i] : 0.f;
-      tc[u] = i < C ? c[(size_t)row * C + i] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (i0 + 64 * u < C) s = fmaf(ta[u], tc[u], s);
-  }
-  s = wave_sum(s);
+  const float s = wave_rowdot(a + (size_t)row * C, c + (size_t)row * C, C, lane);
   if (lane == 0) out[(size_t)row * ostride] = s;
+}
+
+// mmf_analyze_mixed's finish (kernels.h MixedFinishArgs): one wave per batch row, as fusion_kernel --
+// it sits after the join, so its latency is exposed.  A row's list positions come from row_map; a
+// position outside its list counts as absent, and a "both" position only counts with the text and
+// image positions beside it, so every read below is inside its buffer whatever the map holds.
+__global__ __launch_bounds__(256) void mixed_finish_kernel(MixedFinishArgs a) {
+  __shared__ FusionLds L;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  const bool live = row < a.B;
+  int ti = -1, ii = -1, ci = -1;
+  if (live) {
+    ti = a.row_map[(size_t)row * 3];
+    ii = a.row_map[(size_t)row * 3 + 1];
+    ci = a.row_map[(size_t)row * 3 + 2];
+  }
+  const bool has_t = ti >= 0 && ti < a.nT, has_i = ii >= 0 && ii < a.nI;
+  const bool has_c = has_t && has_i && ci >= 0 && ci < a.nC;
+  const bool vault = has_i && a.c_sims != nullptr;
+  float x[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (has_t) { x[0] = a.text2[(size_t)ti * 2]; x[1] = a.text2[(size_t)ti * 2 + 1]; }
+  if (has_i) x[2] = a.deepfake[ii];
+  float top1 = 0.f;
+  int top1_idx = -1;
+  if (vault) {
+    x[4] = a.c_disc[ii];
+    top1 = a.c_sims[(size_t)ii * 5];
+    top1_idx = a.c_idx[(size_t)ii * 5];
+  }
+  if (a.nC > 0) fusion_stage(L, a.w0, a.b0, a.w3, a.b3, a.w5, a.b5, tid);  // (kernel-uniform)
+  // wave-uniform branches: the whole wave works on one row
+  if (has_c) x[3] = wave_rowdot(a.v_emb + (size_t)ii * 512, a.t_emb + (size_t)ci * 512, 512, lane);
+  float tsim = 0.f;
+  // vault_topk_kernel's hit: top-1 above the threshold (a NaN or an empty slot is not)
+  if (has_c && vault && a.title && top1 > a.thresh && top1_idx >= 0)
+    tsim = wave_rowdot(a.t_emb + (size_t)ci * 512, a.title + (size_t)top1_idx * 512, 512, lane);
+  if (live && lane < 5) {
+    if (a.top_sims) a.top_sims[(size_t)row * 5 + lane] = vault ? a.c_sims[(size_t)ii * 5 + lane] : 0.f;
+    if (a.top_idx) a.top_idx[(size_t)row * 5 + lane] = vault ? a.c_idx[(size_t)ii * 5 + lane] : -1;
+  }
+  float p0 = 0.f, p1 = 0.f;
+  if (a.nC > 0) {
+    __syncthreads();
+    fusion_mlp(L, x, wave, lane, &p0, &p1);
+  }
+  if (!live || lane != 0) return;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) a.scores5[(size_t)row * 5 + i] = x[i];
+  if (a.text_sim) a.text_sim[row] = tsim;
+  if (!has_c) {  // misinfo_forensics.py:883-899: text -> misinfo, else max(deepfake, vault_discrepancy)
+    const float fake = fminf(fmaxf(has_t ? x[1] : fmaxf(x[2], x[4]), 0.f), 1.f);
+    p0 = 1.f - fake;
+    p1 = fake;
+  }
+  write_verdict(row, p0, p1, x, a.probs, a.verdict, a.conf, a.rule);
 }
 
 // S[B][N] = Q[B][D] . V[N][D]^T, fp32 (misinfo_forensics.py:446).  Tile 16 queries x 64 rows,
@@ -389,22 +483,7 @@ __global__ __launch_bounds__(256) void vault_topk_kernel(const float* S, int B, 
   }
   if (tsim) {
     float d = 0.f;
-    if (hit && temb && title) {
-      // 8 columns per lane in flight at once (D <= 512), then the same ascending-c fmaf chain
-      for (int c0 = lane; c0 < D; c0 += 512) {
-        float ta[8], tb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int c = c0 + 64 * u;
-          ta[u] = c < D ? temb[(size_t)row * D + c] : 0.f;
-          tb[u] = c < D ? title[(size_t)outi[0] * D + c] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (c0 + 64 * u < D) d = fmaf(ta[u], tb[u], d);
-      }
-      d = wave_sum(d);
-    }
+    if (hit && temb && title) d = wave_rowdot(temb + (size_t)row * D, title + (size_t)outi[0] * D, D, lane);
     if (lane == 0) tsim[row] = d;
   }
 }
@@ -478,6 +557,17 @@ hipError_t launch_fusion(const float* x5, const float* w0, const float* b0, cons
 
 hipError_t launch_rowdot(const float* a, const float* c, float* out, int ostride, int B, int C, hipStream_t s) {
   hipLaunchKernelGGL(rowdot_kernel, dim3((B + 3) / 4), dim3(256), 0, s, a, c, out, ostride, B, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_mixed_finish(const MixedFinishArgs& a, hipStream_t s) {
+  if (a.B <= 0 || !a.row_map || !a.scores5 || !a.probs) return hipErrorInvalidValue;
+  // a list the batch uses needs its buffers (the kernel reads them for every position inside the list)
+  if ((a.nT > 0 && !a.text2) || (a.nI > 0 && (!a.deepfake || !a.v_emb)) ||
+      (a.nC > 0 && (!a.t_emb || !a.w0 || !a.b0 || !a.w3 || !a.b3 || !a.w5 || !a.b5)) ||
+      (a.c_sims && (!a.c_idx || !a.c_disc)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mixed_finish_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

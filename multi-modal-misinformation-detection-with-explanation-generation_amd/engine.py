@@ -14,6 +14,8 @@ from . import hip, io_utils
 from .hip import check, ptr, stream_ptr
 
 SCORE_KEYS = ("ai_score", "misinfo_score", "deepfake_score", "clip_similarity", "vault_discrepancy")
+# the reference's error for a post with no modality (misinfo_forensics.py:793-794)
+NO_INPUT_ERROR = "Provide at least one of: text, image_path, or video_path"
 
 
 def _as_np(v) -> np.ndarray:
@@ -517,6 +519,73 @@ class Engine:
             ptr(img), ptr(img_clip), B, ptr(out["scores"]), ptr(out["text_similarity"]), ptr(out["probs"]),
             ptr(out["verdict"]), ptr(out["confidence"]), ptr(out["rule"]), ptr(out["top_sims"]),
             ptr(out["top_idx"]), stream_ptr()), "mmf_analyze_batch")
+        return out
+
+    def mixed_plan(self, modality):
+        """Host plan of a mixed batch (mmf_mixed_plan): modality per row (bit 0 text, bit 1 image) ->
+        (row_map int32 [B, 3], (nT, nI, nC)).  A row without a modality raises the reference's
+        ValueError (misinfo_forensics.py:793-794)."""
+        m = np.asarray(modality.cpu() if isinstance(modality, torch.Tensor) else modality).reshape(-1)
+        if m.size == 0:
+            raise ValueError("empty batch")
+        if (m == 0).any():
+            raise ValueError(NO_INPUT_ERROR)
+        if ((m < 0) | (m > 3)).any():
+            raise ValueError("modality entries are 1 (text), 2 (image) or 3 (both)")
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+        row_map = np.empty((m.size, 3), np.int32)
+        counts = np.zeros(3, np.int32)
+        check(self.lib.mmf_mixed_plan(m.ctypes.data_as(ctypes.c_void_p), m.size, row_map.ctypes.data_as(ctypes.c_void_p),
+                                      counts.ctypes.data_as(ctypes.c_void_p)), "mmf_mixed_plan")
+        return row_map, tuple(int(c) for c in counts)
+
+    _PLAN_CACHE = 8  # device row maps kept (a serving loop repeats a few modality patterns)
+
+    def _device_plan(self, modality):
+        """mixed_plan with the row map on the device.  The upload of a small pageable array waits for
+        the stream, so the last few plans are kept by their modality bytes: a repeated pattern costs
+        no copy."""
+        m = np.asarray(modality.cpu() if isinstance(modality, torch.Tensor) else modality).reshape(-1)
+        key = m.astype(np.int64).tobytes()
+        cache = self.__dict__.setdefault("_plans", {})
+        hit = cache.pop(key, None)
+        if hit is None:
+            row_map, counts = self.mixed_plan(m)
+            hit = (torch.from_numpy(row_map).to(self.device), counts)
+            while len(cache) >= self._PLAN_CACHE:
+                cache.pop(next(iter(cache)))
+        cache[key] = hit  # (re-inserted last: the oldest entry is dropped first)
+        return hit
+
+    def analyze_mixed(self, modality, rob_ids, rob_mask, clip_ids, clip_mask, img, img_clip=None,
+                      out: Optional[dict] = None) -> dict:
+        """analyze_batch for posts with a text, an image or both (misinfo_forensics.py:790-899) in one
+        launch sequence.  modality [B]: 1 text, 2 image, 3 both.  The inputs are COMPACT: rob_ids /
+        rob_mask hold the nT text rows in batch order, img / img_clip the nI image rows, clip_ids /
+        clip_mask the nC rows with both; a list without rows may be None.  Returns analyze_batch's
+        dict of [B, ...] device tensors in batch order, absent signals 0 (top_idx -1) and the
+        reference's single-modality verdict on the rows that are not pairs."""
+        dmap, (nT, nI, nC) = self._device_plan(modality)
+        B = dmap.shape[0]
+
+        def rows(name, t, n):
+            if n and (t is None or t.shape[0] != n):
+                raise ValueError(f"{name}: expected {n} rows, got {None if t is None else t.shape[0]}")
+            return t if n else None
+        rob_ids = rows("rob_ids", self._i32(rob_ids) if nT else None, nT)
+        rob_mask = rows("rob_mask", self._i32(rob_mask) if nT else None, nT)
+        clip_ids = rows("clip_ids", self._i32(clip_ids) if nC else None, nC)
+        clip_mask = rows("clip_mask", self._i32(clip_mask) if nC else None, nC)
+        img = rows("img", self._u8(img) if nI else None, nI)
+        img_clip = rows("img_clip", self._u8(img_clip), nI) if nI and img_clip is not None else None
+        if out is None:
+            out = self.alloc_outputs(B)
+        check(self.lib.mmf_analyze_mixed(
+            self.h, ptr(dmap), B, nT, nI, nC, ptr(rob_ids), ptr(rob_mask), rob_ids.shape[1] if nT else 0,
+            ptr(clip_ids), ptr(clip_mask), clip_ids.shape[1] if nC else 0, ptr(img), ptr(img_clip),
+            ptr(out["scores"]), ptr(out["text_similarity"]), ptr(out["probs"]), ptr(out["verdict"]),
+            ptr(out["confidence"]), ptr(out["rule"]), ptr(out["top_sims"]), ptr(out["top_idx"]), stream_ptr()),
+            "mmf_analyze_mixed")
         return out
 
     def alloc_outputs(self, B: int) -> dict:

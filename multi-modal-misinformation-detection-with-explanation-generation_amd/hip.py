@@ -46,6 +46,9 @@ SIGNATURES = {
     "mmf_vault_topk": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "mmf_fusion": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "mmf_analyze_batch": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmf_mixed_plan": (_I, [_P, _I, _P, _P]),
+    "mmf_analyze_mixed": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                               _P]),
     "mmf_profile_begin": (_I, [_P]),
     "mmf_profile_end": (_I, [_P, _I, _P, _P, _P, _P]),
     "mmf_profile_kind_name": (ctypes.c_char_p, [_I]),
