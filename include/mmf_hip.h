@@ -187,7 +187,8 @@ int mmf_set_vault_normalized(mmf_handle* h, const float* host_vault_unit, int N,
 int mmf_set_vault_titles(mmf_handle* h, const int32_t* ids, const int32_t* mask, int N, int L, void* stream);
 
 /* search_vault core (misinfo_forensics.py:443-464, 467-484): q fp32 [B, 512] unit image
- * embeddings; top-k (1 <= k <= N; k > 8 needs N <= 16384) similarities fp32 [B, k] and indices
+ * embeddings; top-k (1 <= k <= N; on a vault of more than 16384 rows k <= 64 and
+ * ceil(N / 16384) * k <= 16384) similarities fp32 [B, k] and indices
  * int32 [B, k] in np.argsort(sims)[-k:][::-1] order (descending; NaN rows first, exact ties by
  * descending index);
  * discrepancy fp32 [B] = top1 > thresh ? top1 : 0; optional text_emb fp32 [B, 512] unit caption
@@ -289,6 +290,9 @@ const char* mmf_profile_kind_name(int kind);
  *   "qkv_attn"       1: RoBERTa L = 128: attention in the QKV GEMM's epilogue
  *   "vault_ref"      0: diagnostic: vault similarities on the VALU kernel, top-k by full sort (the
  *                       reference kernels the production MFMA / register top-k kernels equal bit for bit)
+ *   "vault_fused"    2: vault search without the [B, N] similarity matrix (fused similarity + top-k
+ *                       kernel, bit-identical results): 0 the two-kernel path, 1 fused wherever
+ *                       top_k <= 8, 2 fused iff the vault has more than 16384 rows
  *   "mt_enqueue"    64: batches of <= this many pairs: towers enqueued by host threads side by side
  *   "last_q1"        1: compact last encoder layers (bit 1 RoBERTa, bit 2 CLIP towers)
  *   "after_text"    12: towers of the concurrent step that start once RoBERTa is done (bitmask as
@@ -303,6 +307,19 @@ int mmf_set_option(mmf_handle* h, const char* name, int value);
 int mmf_get_option(mmf_handle* h, const char* name, int* value);
 /* Device bytes currently owned by the handle (weights, workspaces, vault). */
 int64_t mmf_device_bytes(mmf_handle* h);
+
+/* Low-level vault search over caller-owned device memory (no handle): what mmf_vault_topk computes, by
+ * the fused similarity + top-k kernels, for any bank of unit rows.  q_unit fp32 [B, D], bank_unit fp32
+ * [N, D]; D must be 512 and k in 1..8 (k > N pads slots N.. with similarity -inf and index -1);
+ * outputs as mmf_vault_topk, discrepancy at discrepancy[b * disc_stride]; title_bank fp32 [N, D] or
+ * NULL.  ws: mmf_vault_search_ws_bytes(B, k, nblocks) bytes of device scratch.  nblocks = vault
+ * partitions (blocks per 64 queries, each walking a contiguous range of 64-row tiles; 0 = automatic,
+ * at most 256); the result does not depend on it. */
+int64_t mmf_vault_search_ws_bytes(int B, int k, int nblocks);
+int mmf_vault_search_rows(const float* q_unit, const float* bank_unit, int B, int N, int D, int k, float thresh,
+                          float* sims, int32_t* idx, float* discrepancy, int disc_stride, const float* text_emb,
+                          const float* title_bank, float* text_sim, void* ws, int64_t ws_bytes, int nblocks,
+                          void* stream);
 
 /* Low-level op exported for unit tests of the GEMM kernel: C = act(A @ W^T + bias) + residual.
  * A fp16 [M,K] (lda), W fp16 [N,K] (ldw), bias fp32 [N] or NULL, residual fp32 [M,N] (ldc) or NULL,

@@ -50,7 +50,7 @@ const OptName kOptNames[] = {
     {"pw32_mfma", &Options::pw32_mfma, "MMF_PW32_MFMA"},
     {"effnet_chunks", &Options::effnet_chunks, "MMF_EFFNET_CHUNKS"}, {"dw_cw32", &Options::dw_cw32, "MMF_DW_CW32"},
     {"diag_skip", &Options::diag_skip, "MMF_DIAG_SKIP"}, {"qkv_attn", &Options::qkv_attn, "MMF_QKV_ATTN"},
-    {"vault_ref", &Options::vault_ref, "MMF_VAULT_REF"},
+    {"vault_ref", &Options::vault_ref, "MMF_VAULT_REF"}, {"vault_fused", &Options::vault_fused, "MMF_VAULT_FUSED"},
     {"mt_enqueue", &Options::mt_enqueue, "MMF_MT_ENQUEUE"}, {"last_q1", &Options::last_q1, "MMF_LAST_Q1"},
     {"after_text", &Options::after_text, "MMF_AFTER_TEXT"},
 };
@@ -100,6 +100,51 @@ EnqueuePool& ensure_pool(mmf_handle* h) {
   return *h->pool;
 }
 
+// The vault served by the fused similarity + top-k kernels (option vault_fused; top_k <= 8)
+constexpr int kVaultChunk = 16384;  // rows the LDS sort kernel ranks at once (top_k > 8)
+bool vault_is_fused(const mmf_handle* h) {
+  return h->opt.vault_fused == 1 || (h->opt.vault_fused == 2 && h->vault_n > kVaultChunk);
+}
+
+// Top-k of q[B][512] against the handle's vault, behind mmf_vault_topk and both analysis tails.  Every
+// path ranks bit-identical similarities under one total order, so the outputs do not depend on the path:
+// the fused kernels (no similarity matrix), the similarity + top-k kernel pair over S[B][N], or, for
+// top_k > 8 on more than 16384 rows, the pair per 16384-row chunk and a final sort of the chunks' k each.
+// The workspaces were sized by ensure_sims (mmf_reserve, the vault setters, mmf_set_option).
+int vault_search(mmf_handle* h, const float* q, int B, int k, float thresh, float* sims, int32_t* idx, float* disc,
+                 int disc_stride, const float* temb, float* tsim, hipStream_t s) {
+  Workspace& w = h->ws;
+  const int N = h->vault_n, ref = h->opt.vault_ref;
+  const char* unreserved = "vault search workspace not reserved (call mmf_reserve)";
+  if (k <= 8 && vault_is_fused(h)) {
+    if (!w.vs_ws) return fail(MMF_EINVAL, "%s", unreserved);
+    HIPCHK(launch_vault_search(q, h->vault, B, N, k, thresh, sims, idx, disc, disc_stride, temb, h->vault_title, tsim,
+                               w.vs_ws, 0, s));
+    return 0;
+  }
+  if (k <= 8 || N <= kVaultChunk) {  // (the sort kernel of top_k > 8 holds at most kVaultChunk rows)
+    if (w.s_cap_n < N) return fail(MMF_EINVAL, "%s", unreserved);
+    HIPCHK(launch_vault_sims(q, h->vault, w.s_sims, B, N, 512, s, ref));
+    HIPCHK(launch_vault_topk(w.s_sims, B, N, k, thresh, sims, idx, disc, disc_stride, temb, h->vault_title, 512, tsim,
+                             s, ref));
+    return 0;
+  }
+  const int chunks = (N + kVaultChunk - 1) / kVaultChunk;
+  if (k > 64 || (long long)chunks * k > kVaultChunk)
+    return fail(MMF_EINVAL, "top_k = %d on a vault of %d rows: more than 16384 rows take top_k <= 64 and "
+                            "ceil(N / 16384) * top_k <= 16384", k, N);
+  if (w.s_cap_n < kVaultChunk || w.c_chunks < chunks) return fail(MMF_EINVAL, "%s", unreserved);
+  for (int c = 0; c < chunks; ++c) {
+    const int n = std::min(kVaultChunk, N - c * kVaultChunk);
+    HIPCHK(launch_vault_sims(q, h->vault + (size_t)c * kVaultChunk * 512, w.s_sims, B, n, 512, s, ref));
+    HIPCHK(launch_vault_topk(w.s_sims, B, n, k, thresh, w.c_sims + (size_t)c * B * k, w.c_idx + (size_t)c * B * k,
+                             nullptr, 1, nullptr, nullptr, 512, nullptr, s, ref));
+  }
+  HIPCHK(launch_vault_sort_cand(w.c_sims, w.c_idx, chunks, kVaultChunk, B, k, thresh, sims, idx, disc, disc_stride, temb,
+                                h->vault_title, 512, tsim, s));
+  return 0;
+}
+
 // after the towers joined: CLIP cosine, vault top-5, fusion (mmf_analyze_batch's last part)
 int analyze_tail(mmf_handle* h, int B, float* scores5, float* text_sim, float* probs2, int32_t* verdict, float* conf,
                  int32_t* rule, float* top_sims, int32_t* top_idx, hipStream_t s) {
@@ -107,9 +152,7 @@ int analyze_tail(mmf_handle* h, int B, float* scores5, float* text_sim, float* p
   HIPCHK(launch_rowdot(w.v_emb, w.t_emb, scores5 + 3, 5, B, 512, s));
   if (h->ready & RDY_VAULT) {
     ProfScope ps(h, s, PK_VAULT, 2.0 * B * h->vault_n * 512, (double)h->vault_n * 512 * 4 + (double)B * h->vault_n * 8);
-    HIPCHK(launch_vault_sims(w.v_emb, h->vault, w.s_sims, B, h->vault_n, 512, s, h->opt.vault_ref));
-    HIPCHK(launch_vault_topk(w.s_sims, B, h->vault_n, 5, 0.85f, top_sims, top_idx, scores5 + 4, 5, w.t_emb,
-                             h->vault_title, 512, text_sim, s, h->opt.vault_ref));
+    CHK(vault_search(h, w.v_emb, B, 5, 0.85f, top_sims, top_idx, scores5 + 4, 5, w.t_emb, text_sim, s));
   } else {
     HIPCHK(launch_fill_strided(scores5 + 4, 5, B, 0.f, s));
     if (text_sim) HIPCHK(hipMemsetAsync(text_sim, 0, (size_t)B * 4, s));
@@ -216,9 +259,7 @@ int mixed_tail(mmf_handle* h, const int32_t* row_map, int B, int nT, int nI, int
   const bool vault = nI > 0 && (h->ready & RDY_VAULT);
   if (vault) {
     ProfScope ps(h, s, PK_VAULT, 2.0 * nI * h->vault_n * 512, (double)h->vault_n * 512 * 4 + (double)nI * h->vault_n * 8);
-    HIPCHK(launch_vault_sims(w.v_emb, h->vault, w.s_sims, nI, h->vault_n, 512, s, h->opt.vault_ref));
-    HIPCHK(launch_vault_topk(w.s_sims, nI, h->vault_n, 5, 0.85f, w.m_sims, w.m_idx, w.m_disc, 1, nullptr, nullptr, 512,
-                             nullptr, s, h->opt.vault_ref));
+    CHK(vault_search(h, w.v_emb, nI, 5, 0.85f, w.m_sims, w.m_idx, w.m_disc, 1, nullptr, nullptr, s));
   }
   MixedFinishArgs a{};
   a.row_map = row_map;
@@ -280,12 +321,34 @@ int ensure_mode_ws(mmf_handle* h) {
   return 0;
 }
 
+// The vault search workspaces (group AG_SIMS) for the reserved batch, the vault and option vault_fused,
+// set up outside any launch sequence (mmf_reserve, the vault setters, mmf_set_option).  A vault that is
+// served fused needs no S[cap_b][N]: it gets the candidate workspace, and above 16384 rows one chunk
+// of S plus the per-chunk results for top_k > 8 -- none of which grows with N (the chunk results: 512
+// bytes per query and 16384 rows).
 int ensure_sims(mmf_handle* h) {
   if (!h->vault_n || !h->cap_b) return 0;
-  if (h->ws.s_cap_n >= h->vault_n) return 0;
+  Workspace& w = h->ws;
+  const int N = h->vault_n;
+  const bool fused = vault_is_fused(h), large = N > kVaultChunk;
+  const int need_n = fused && large ? kVaultChunk : N;
+  const int need_chunks = large ? (N + kVaultChunk - 1) / kVaultChunk : 0;
+  if (w.s_cap_n == need_n && (w.vs_ws != nullptr) == fused && w.c_chunks == need_chunks) return 0;
   CHK(free_group(h, AG_SIMS));
-  CHK(dev_alloc(h, &h->ws.s_sims, (size_t)h->cap_b * h->vault_n, AG_SIMS));
-  h->ws.s_cap_n = h->vault_n;
+  w.s_sims = nullptr; w.vs_ws = nullptr; w.c_sims = nullptr; w.c_idx = nullptr;
+  w.s_cap_n = w.c_chunks = 0;
+  CHK(dev_alloc(h, &w.s_sims, (size_t)h->cap_b * need_n, AG_SIMS));
+  w.s_cap_n = need_n;
+  if (fused) {
+    uint8_t* p;
+    CHK(dev_alloc(h, &p, vault_search_ws_bytes(h->cap_b, 8, 0), AG_SIMS));
+    w.vs_ws = p;
+  }
+  if (need_chunks) {
+    CHK(dev_alloc(h, &w.c_sims, (size_t)need_chunks * h->cap_b * 64, AG_SIMS));
+    CHK(dev_alloc(h, &w.c_idx, (size_t)need_chunks * h->cap_b * 64, AG_SIMS));
+    w.c_chunks = need_chunks;
+  }
   return 0;
 }
 
@@ -596,14 +659,9 @@ int mmf_vault_topk(mmf_handle* h, const float* q, int B, int k, float thresh, fl
   if (!h || !q) return fail(MMF_EINVAL, "null argument");
   if (!(h->ready & RDY_VAULT)) return fail(MMF_EINVAL, "vault not loaded");
   if (k < 1 || k > h->vault_n) return fail(MMF_EINVAL, "top_k must be in [1, N=%d]", h->vault_n);
-  if (k > 8 && h->vault_n > 16384) return fail(MMF_EINVAL, "top_k > 8 needs a vault of <= 16384 rows");
   CHK(check_cap(h, B, 1, 1));
   HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(launch_vault_sims(q, h->vault, h->ws.s_sims, B, h->vault_n, 512, s, h->opt.vault_ref));
-  HIPCHK(launch_vault_topk(h->ws.s_sims, B, h->vault_n, k, thresh, sims, idx, disc, 1, temb, h->vault_title, 512,
-                           tsim, s, h->opt.vault_ref));
-  return 0;
+  return vault_search(h, q, B, k, thresh, sims, idx, disc, 1, temb, tsim, (hipStream_t)stream);
 }
 
 int mmf_fusion(mmf_handle* h, const float* x5, int B, float* probs, int32_t* verdict, float* conf, int32_t* rule,
@@ -732,6 +790,7 @@ int mmf_set_option(mmf_handle* h, const char* name, int value) {
       o.*(n.field) = value;
       if (h) {
         (void)hipSetDevice(h->device);
+        if (!strcmp(name, "vault_fused")) CHK(ensure_sims(h));  // (and the vault's, this one)
         return ensure_mode_ws(h);  // (precision modes: their workspaces follow the selection)
       }
       return 0;
@@ -851,6 +910,30 @@ int mmf_attention_f16(const void* qkv, const int32_t* mask, void* out, int B, in
   hipError_t e = launch_attention((const f16_t*)qkv, 3 * H * 64, mask, (f16_t*)out, H * 64, B, L, H, causal,
                                   (hipStream_t)stream);
   if (e != hipSuccess) return fail(MMF_EIO, "attention: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int64_t mmf_vault_search_ws_bytes(int B, int k, int nblocks) {
+  if (B < 1 || k < 1 || k > 8 || nblocks < 0 || nblocks > 65535) return 0;
+  return (int64_t)vault_search_ws_bytes(B, k, nblocks);
+}
+
+int mmf_vault_search_rows(const float* q_unit, const float* bank_unit, int B, int N, int D, int k, float thresh,
+                          float* sims, int32_t* idx, float* disc, int disc_stride, const float* text_emb,
+                          const float* title_bank, float* text_sim, void* ws, int64_t ws_bytes, int nblocks,
+                          void* stream) {
+  if (!q_unit || !bank_unit || !ws) return fail(MMF_EINVAL, "null argument");
+  if (B < 1 || N < 1 || D != 512) return fail(MMF_EINVAL, "mmf_vault_search_rows: need B > 0, N > 0 rows of D = 512");
+  if (k < 1 || k > 8) return fail(MMF_EINVAL, "mmf_vault_search_rows: top_k must be in [1, 8] (got %d)", k);
+  if (nblocks < 0 || nblocks > 65535) return fail(MMF_EINVAL, "mmf_vault_search_rows: nblocks must be in [0, 65535]");
+  if (disc && disc_stride < 1) return fail(MMF_EINVAL, "mmf_vault_search_rows: disc_stride must be >= 1");
+  const int64_t need = mmf_vault_search_ws_bytes(B, k, nblocks);
+  if (ws_bytes < need)
+    return fail(MMF_EINVAL, "mmf_vault_search_rows: workspace of %lld bytes, needs %lld", (long long)ws_bytes,
+                (long long)need);
+  hipError_t e = launch_vault_search(q_unit, bank_unit, B, N, k, thresh, sims, idx, disc, disc_stride, text_emb,
+                                     title_bank, text_sim, ws, nblocks, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MMF_EIO, "vault search: %s", hipGetErrorString(e));
   return 0;
 }
 

@@ -117,8 +117,13 @@ struct Workspace {
   float *sk_text = nullptr, *sk_vit = nullptr, *sk_ctext = nullptr;
   size_t sk_elems = 0;
   // vault
-  float* s_sims = nullptr;
+  float* s_sims = nullptr;  // S[cap_b][s_cap_n]: the whole vault, or one 16384-row chunk of a large fused one
   int s_cap_n = 0;
+  void* vs_ws = nullptr;    // fused search candidates (vault_search_ws_bytes(cap_b, 8, 0)), while the vault is served fused
+  // top_k > 8 on a vault of more than 16384 rows: per-chunk results [c_chunks][cap_b][64]
+  float* c_sims = nullptr;
+  int32_t* c_idx = nullptr;
+  int c_chunks = 0;
   // mmf_analyze_mixed: the towers' compact results (text scores [nT][2], deepfake [nI], vault top-5
   // and discrepancy of the nI image rows) that its finish kernel gathers into batch order
   float *m_text = nullptr, *m_eff = nullptr, *m_sims = nullptr, *m_disc = nullptr;
@@ -156,6 +161,8 @@ struct Options {
   int diag_skip = 0;    // diagnostic: towers mmf_analyze_batch leaves out (bitmask; measurement only)
   int vault_ref = 0;    // diagnostic: vault similarities on the VALU kernel and top-k by full sort (the
                         // reference kernels the production ones are bit-identical to)
+  int vault_fused = 2;  // vault search without the similarity matrix (misc.hip vault_search_partial_kernel): 0 = the
+                        // two-kernel path, 1 = fused wherever top_k <= 8, 2 = fused iff the vault has > 16384 rows
   int after_text = 12;  // towers of the concurrent B > mt_enqueue step that start only once RoBERTa is done
                         // (bitmask as diag_skip: 2 EfficientNet, 4 CLIP text, 8 ViT)
 };

@@ -175,6 +175,19 @@ hipError_t launch_vault_sims(const float* q, const float* v, float* S, int B, in
 hipError_t launch_vault_topk(const float* S, int B, int N, int k, float thresh, float* sims, int32_t* idx,
                              float* disc, int disc_stride, const float* text_emb, const float* title_emb, int D,
                              float* text_sim, hipStream_t s, int ref = 0);
+// the same result without S (option vault_fused, mmf_vault_search_rows): D = 512, k in 1..8; ws holds
+// vault_search_ws_bytes(B, k, nblocks) bytes of per-block candidates; nblocks 0 = vault_search_blocks' choice
+int vault_search_blocks(int B, int N, int nblocks);
+size_t vault_search_ws_bytes(int B, int k, int nblocks);
+hipError_t launch_vault_search(const float* q, const float* v, int B, int N, int k, float thresh, float* sims,
+                               int32_t* idx, float* disc, int disc_stride, const float* text_emb,
+                               const float* title_emb, float* text_sim, void* ws, int nblocks, hipStream_t s);
+// final ranking of [chunks][B][k] per-chunk top-k results (launch_vault_topk outputs with chunk-local
+// indices, chunk c = vault rows c * chunk_rows ..): chunks * k <= 16384
+hipError_t launch_vault_sort_cand(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
+                                  float thresh, float* sims, int32_t* idx, float* disc, int disc_stride,
+                                  const float* text_emb, const float* title_emb, int D, float* text_sim,
+                                  hipStream_t s);
 
 // EfficientNet-B0 pieces (NHWC fp16 activations)
 hipError_t launch_effnet_stem(const uint8_t* img, const float* w, const float* bias, f16_t* out, int B,

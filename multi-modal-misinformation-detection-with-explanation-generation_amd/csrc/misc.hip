@@ -1,6 +1,8 @@
 // Small fp32 kernels at the ends of the path: the RoBERTa dual heads, the FusionJudge MLP with
 // verdict / explanation rule, cosine rows, and the Truth-Vault search (similarities + top-k).
 // These are latency/L2-bound: they run in exact fp32 like the reference.
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -536,6 +538,276 @@ __global__ __launch_bounds__(1024) void vault_sort_topk_kernel(const float* S, i
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fused similarity + top-k (mmf_vault_search_rows, option vault_fused): the result of
+// vault_sims_mfma_kernel + vault_topk_kernel without S[B][N].  Every similarity is the same chain
+// (v_mfma_f32_16x16x4_f32 over k = 0 .. 511 in order from 0, vault rows = A operand) and the ranking
+// the same `better` order, so the selected (value, index) pairs are bit-identical.
+//
+// Partial kernel: grid (nblocks, ceil(B / 64)).  A block keeps its 64 queries in LDS for the whole
+// kernel (four 16-query groups x 32 chunk images in vault_sims_mfma_kernel's k-transposed layout,
+// 128 KB; rows past B are zero) and walks a contiguous range of 64-row vault tiles; wave w owns rows
+// 16 w .. 16 w + 15 of each tile.  A wave fetches its 16 x 512 slice once per tile with 16-B loads
+// (the next tile's loads are in flight while this one is consumed -- they are the only global loads
+// of the loop, so nothing queues behind them), turns it into the MFMA's A layout through a 4 KB
+// wave-private LDS scratch and holds it in 128 registers; the query groups then stream past it two
+// at a time, one accumulator each, so the 40-cycle dependent MFMA latency hides behind the other
+// chain's 32-cycle issue.  The loop has no block barrier.  Each lane keeps a register top-K per query
+// group (its query 16 j + lane % 16, the rows it saw); at the end the 16 lists of a query (4 waves x
+// 4 lane groups) meet in LDS and one thread per query writes the block's K candidates.
+constexpr int kVsQ = 64;        // queries per block
+constexpr int kVsAuto = 256;    // blocks of the automatic grid (one per CU: the block owns the LDS)
+
+template <int K>
+MMF_DEV void topk_insert(float (&tv)[K], int (&ti)[K], float v, int vi) {
+  if (better(v, vi, tv[K - 1], ti[K - 1])) {
+    tv[K - 1] = v; ti[K - 1] = vi;
+#pragma unroll
+    for (int i = K - 1; i > 0; --i) {
+      if (better(tv[i], ti[i], tv[i - 1], ti[i - 1])) {
+        const float a = tv[i]; tv[i] = tv[i - 1]; tv[i - 1] = a;
+        const int b = ti[i]; ti[i] = ti[i - 1]; ti[i - 1] = b;
+      }
+    }
+  }
+}
+
+// the wave's top K of its lanes' sorted lists (K rounds of a wave arg-max over the heads, the winning
+// lane pops), valid on every lane
+template <int K>
+MMF_DEV void wave_topk(float (&tv)[K], int (&ti)[K], float (&outv)[K], int (&outi)[K]) {
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    float bv = tv[0];
+    int bi = ti[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    outv[t] = bv; outi[t] = bi;
+    if (ti[0] == bi) {
+#pragma unroll
+      for (int i = 0; i < K - 1; ++i) { tv[i] = tv[i + 1]; ti[i] = ti[i + 1]; }
+      tv[K - 1] = -INFINITY; ti[K - 1] = -1;
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void vault_search_partial_kernel(const float* __restrict__ q,
+                                                                   const float* __restrict__ v, int B, int N,
+                                                                   float* __restrict__ cv, int* __restrict__ ci) {
+  __shared__ __attribute__((aligned(16))) float qs[4][32][16 * 16];  // [group][chunk][vq_off image]
+  __shared__ __attribute__((aligned(16))) float ts[4][4][16 * 16];   // per wave: four chunk images
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+  const int tiles = (N + 63) / 64, nb = gridDim.x;
+  const int t0 = (int)((long long)blockIdx.x * tiles / nb), t1 = (int)((long long)(blockIdx.x + 1) * tiles / nb);
+  const int q0 = blockIdx.y * kVsQ;
+  const int ng = min(4, (B - q0 + 15) / 16);  // query groups of this block (>= 1)
+  // the block's queries -> LDS: thread = (row tid / 4, k quad tid % 4) of a 16 x 16 chunk, as the
+  // similarity kernel's loader; wave j stages group j
+  {
+    const int lr = lane >> 2, lc = lane & 3, b = q0 + wave * 16 + lr;
+    const float* qp = q + (size_t)min(b, B - 1) * 512 + lc * 4;
+#pragma unroll 4
+    for (int h = 0; h < 32; ++h) {
+      float4 x = *reinterpret_cast<const float4*>(qp + 16 * h);
+      if (b >= B) x = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float xv[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) qs[wave][h][vq_off(lr, e) + lc] = xv[e];
+    }
+  }
+  __syncthreads();
+  float tv[4][K];
+  int ti[4][K];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < K; ++i) { tv[j][i] = -INFINITY; ti[j][i] = -1; }
+  // the wave's slice of a tile: lane = (row lane / 4, k quad lane % 4), 32 chunks
+  const int lr = lane >> 2, lc = lane & 3;
+  float4 rv[32];
+  auto gload = [&](int t) {
+    const float* vp = v + (size_t)min(t * 64 + wave * 16 + lr, N - 1) * 512 + lc * 4;  // clamped: loaded, never ranked
+#pragma unroll
+    for (int h = 0; h < 32; ++h) rv[h] = *reinterpret_cast<const float4*>(vp + 16 * h);
+  };
+  if (t0 < t1) gload(t0);
+  for (int t = t0; t < t1; ++t) {
+    // A layout through the wave's scratch, four chunks a round (the LDS serves a wave's accesses in
+    // order; the wave barriers keep the compiler from moving them across each other)
+    float4 a[32];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float4 x = rv[4 * r + c];
+        const float xv[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ts[wave][c][vq_off(lr, e) + lc] = xv[e];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int c = 0; c < 4; ++c) a[4 * r + c] = *reinterpret_cast<const float4*>(&ts[wave][c][vq_off(fr, fg)]);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (t + 1 < t1) gload(t + 1);
+    const int n = t * 64 + wave * 16 + fg * 4;  // lane: rows n .. n + 3 of query 16 j + fr
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (2 * p >= ng) break;  // (uniform per block)
+      f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int h = 0; h < 32; ++h) {
+        const float4 x0 = *reinterpret_cast<const float4*>(&qs[2 * p][h][vq_off(fr, fg)]);
+        const float4 x1 = *reinterpret_cast<const float4*>(&qs[2 * p + 1][h][vq_off(fr, fg)]);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].x, x0.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].x, x1.x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].y, x0.y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].y, x1.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].z, x0.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].z, x1.z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].w, x0.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].w, x1.w, acc1, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (n + r < N) topk_insert<K>(tv[2 * p], ti[2 * p], rank_key(acc0[r]), n + r);
+      if (2 * p + 1 < ng) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < N) topk_insert<K>(tv[2 * p + 1], ti[2 * p + 1], rank_key(acc1[r]), n + r);
+      }
+    }
+  }
+  // the 16 lists of a query -> LDS (over the query images, which every wave is done with), one
+  // thread per query selects the block's K
+  __syncthreads();
+  float* lv = &qs[0][0][0];                                  // [source 16][K][query 64]
+  int* li = reinterpret_cast<int*>(&qs[0][0][0]) + 16 * K * kVsQ;
+  const int src = wave * 4 + fg;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      lv[(src * K + i) * kVsQ + 16 * j + fr] = tv[j][i];
+      li[(src * K + i) * kVsQ + 16 * j + fr] = ti[j][i];
+    }
+  __syncthreads();
+  if (tid < kVsQ && q0 + tid < B) {
+    float bv[K];
+    int bi[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) { bv[i] = -INFINITY; bi[i] = -1; }
+    for (int c = 0; c < 16 * K; ++c) {
+      const int vi = li[c * kVsQ + tid];
+      if (vi >= 0) topk_insert<K>(bv, bi, lv[c * kVsQ + tid], vi);
+    }
+    const size_t o = ((size_t)blockIdx.x * B + q0 + tid) * K;
+#pragma unroll
+    for (int i = 0; i < K; ++i) { cv[o + i] = bv[i]; ci[o + i] = bi[i]; }
+  }
+}
+
+// Merge kernel: one wave per query ranks the nblocks * K candidates (keys, as the partial kernel
+// left them) and runs vault_topk_kernel's epilogue.
+template <int K>
+__global__ __launch_bounds__(64) void vault_search_merge_kernel(const float* __restrict__ cv, const int* __restrict__ ci,
+                                                                int nblocks, int B, float thresh, float* sims,
+                                                                int32_t* idx, float* disc, int disc_stride,
+                                                                const float* temb, const float* title, int D,
+                                                                float* tsim) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  float tv[K], outv[K];
+  int ti[K], outi[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) { tv[i] = -INFINITY; ti[i] = -1; }
+  for (int c = lane; c < nblocks * K; c += 64) {
+    const size_t o = ((size_t)(c / K) * B + row) * K + c % K;
+    const int vi = ci[o];
+    if (vi >= 0) topk_insert<K>(tv, ti, cv[o], vi);
+  }
+  wave_topk<K>(tv, ti, outv, outi);
+  const bool hit = outv[0] > thresh && outv[0] != INFINITY;  // NaN > thresh is false
+  if (lane == 0) {
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      if (sims) sims[(size_t)row * K + t] = unkey(outv[t]);
+      if (idx) idx[(size_t)row * K + t] = outi[t];
+    }
+    if (disc) disc[(size_t)row * disc_stride] = hit ? outv[0] : 0.f;
+  }
+  if (tsim) {
+    float d = 0.f;
+    if (hit && temb && title) d = wave_rowdot(temb + (size_t)row * D, title + (size_t)outi[0] * D, D, lane);
+    if (lane == 0) tsim[row] = d;
+  }
+}
+
+// top-k for 8 < k <= 64 on a vault of more than 16384 rows: the vault is walked in chunks of 16384
+// rows, each through the similarity and sort kernels above into [chunk][B][k] candidates (similarities
+// with NaN restored, chunk-local indices, -1 padding); this kernel sorts a query's chunks * k <= P
+// candidates under the same order and runs the sort kernel's epilogue.
+template <int P>
+__global__ __launch_bounds__(1024) void vault_sort_cand_kernel(const float* cs, const int32_t* cidx, int chunks,
+                                                               int chunk_rows, int B, int k, float thresh, float* sims,
+                                                               int32_t* idx, float* disc, int disc_stride,
+                                                               const float* temb, const float* title, int D,
+                                                               float* tsim) {
+  __shared__ float key[P];
+  __shared__ int id[P];
+  const int row = blockIdx.x, tid = threadIdx.x, n = chunks * k;
+  for (int i = tid; i < P; i += 1024) {
+    float kv = -INFINITY;
+    int ki = -1;
+    if (i < n) {
+      const int c = i / k;
+      const size_t o = ((size_t)c * B + row) * k + i % k;
+      const int li = cidx[o];
+      if (li >= 0) { kv = rank_key(cs[o]); ki = c * chunk_rows + li; }
+    }
+    key[i] = kv;
+    id[i] = ki;
+  }
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < P / 2; i += 1024) {
+        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const float a = key[lo], b = key[hi];
+        const int ia = id[lo], ib = id[hi];
+        if (desc ? better(b, ib, a, ia) : better(a, ia, b, ib)) {
+          key[lo] = b; key[hi] = a;
+          id[lo] = ib; id[hi] = ia;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const bool hit = key[0] > thresh && key[0] != INFINITY;
+  for (int t = tid; t < k; t += 1024) {
+    if (sims) sims[(size_t)row * k + t] = unkey(key[t]);
+    if (idx) idx[(size_t)row * k + t] = id[t];
+  }
+  if (tid == 0 && disc) disc[(size_t)row * disc_stride] = hit ? key[0] : 0.f;
+  if (tsim && tid < 64) {
+    float d = 0.f;
+    if (hit && temb && title) {
+      for (int c = tid; c < D; c += 64) d = fmaf(temb[(size_t)row * D + c], title[(size_t)id[0] * D + c], d);
+      d = wave_sum(d);
+    }
+    if (tid == 0) tsim[row] = d;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_text_heads(const float* x, int row_stride, const float* w1a, const float* b1a, const float* w2a,
@@ -619,6 +891,53 @@ hipError_t launch_vault_topk(const float* S, int B, int N, int k, float thresh, 
   }
 #undef TOPK_CASE
   return hipGetLastError();
+}
+
+int vault_search_blocks(int B, int N, int nblocks) {
+  if (nblocks > 0) return nblocks;
+  const int tiles = (N + 63) / 64, gy = (B + kVsQ - 1) / kVsQ;
+  return std::max(1, std::min(tiles, kVsAuto / gy));
+}
+
+size_t vault_search_ws_bytes(int B, int k, int nblocks) {
+  return (size_t)(nblocks > 0 ? nblocks : kVsAuto) * B * k * (sizeof(float) + sizeof(int32_t));
+}
+
+hipError_t launch_vault_search(const float* q, const float* v, int B, int N, int k, float thresh, float* sims,
+                               int32_t* idx, float* disc, int disc_stride, const float* text_emb,
+                               const float* title_emb, float* text_sim, void* ws, int nblocks, hipStream_t s) {
+  if (B < 1 || N < 1 || k < 1 || k > 8 || nblocks < 0 || !ws) return hipErrorInvalidValue;
+  const int nb = vault_search_blocks(B, N, nblocks);
+  float* cv = (float*)ws;
+  int* ci = (int*)(cv + (size_t)nb * B * k);
+  const dim3 grid(nb, (B + kVsQ - 1) / kVsQ);
+#define SEARCH_CASE(KK)                                                                                          \
+  case KK:                                                                                                       \
+    hipLaunchKernelGGL(vault_search_partial_kernel<KK>, grid, dim3(256), 0, s, q, v, B, N, cv, ci);             \
+    hipLaunchKernelGGL(vault_search_merge_kernel<KK>, dim3(B), dim3(64), 0, s, cv, ci, nb, B, thresh, sims, idx, \
+                       disc, disc_stride, text_emb, title_emb, 512, text_sim);                                   \
+    break;
+  switch (k) {
+    SEARCH_CASE(1) SEARCH_CASE(2) SEARCH_CASE(3) SEARCH_CASE(4) SEARCH_CASE(5) SEARCH_CASE(6) SEARCH_CASE(7) SEARCH_CASE(8)
+  }
+#undef SEARCH_CASE
+  return hipGetLastError();
+}
+
+hipError_t launch_vault_sort_cand(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
+                                  float thresh, float* sims, int32_t* idx, float* disc, int disc_stride,
+                                  const float* text_emb, const float* title_emb, int D, float* text_sim,
+                                  hipStream_t s) {
+  if (chunks < 1 || k < 1 || B < 1) return hipErrorInvalidValue;
+#define CAND_CASE(PP)                                                                                              \
+  if ((long long)chunks * k <= PP) {                                                                               \
+    hipLaunchKernelGGL(vault_sort_cand_kernel<PP>, dim3(B), dim3(1024), 0, s, cs, cidx, chunks, chunk_rows, B, k,  \
+                       thresh, sims, idx, disc, disc_stride, text_emb, title_emb, D, text_sim);                    \
+    return hipGetLastError();                                                                                      \
+  }
+  CAND_CASE(2048) CAND_CASE(16384)
+#undef CAND_CASE
+  return hipErrorInvalidValue;
 }
 
 namespace {

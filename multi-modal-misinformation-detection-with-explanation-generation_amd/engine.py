@@ -494,6 +494,32 @@ class Engine:
                                       ptr(text_emb), ptr(tsim), stream_ptr()), "mmf_vault_topk")
         return sims, idx, disc, tsim
 
+    def search_rows(self, q_unit, bank, k: int = 5, thresh: float = 0.85, text_emb=None, title_bank=None,
+                    nblocks: int = 0):
+        """Top-k of unit queries [B, 512] over ANY device-resident bank [N, 512] of rows (used as they
+        are: no renormalisation), by the fused similarity + top-k kernels (mmf_vault_search_rows: no
+        [B, N] matrix; k in 1..8, slots past N hold index -1).  Returns (sims [B, k], idx [B, k], disc [B],
+        tsim [B]) as vault_topk does; ``title_bank`` [N, 512] with ``text_emb`` [B, 512] gives tsim.
+        ``nblocks``: vault partitions (0 = automatic; the result does not depend on it)."""
+        q = torch.as_tensor(q_unit, dtype=torch.float32).to(self.device).contiguous()
+        if not (torch.is_tensor(bank) and bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous()):
+            raise ValueError("bank must be a contiguous float32 tensor on the device")
+        if q.dim() != 2 or bank.dim() != 2 or q.shape[1] != bank.shape[1]:
+            raise ValueError(f"q_unit {tuple(q.shape)} and bank {tuple(bank.shape)} must be [B, D] and [N, D]")
+        B, N, D = q.shape[0], bank.shape[0], bank.shape[1]
+        need = int(self.lib.mmf_vault_search_ws_bytes(B, k, nblocks))
+        ws = getattr(self, "_search_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._search_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        sims, idx = self._f32(B, k), torch.empty((B, k), dtype=torch.int32, device=self.device)
+        disc, tsim = self._f32(B), self._f32(B)
+        if text_emb is not None:
+            text_emb = torch.as_tensor(text_emb, dtype=torch.float32).to(self.device).contiguous()
+        check(self.lib.mmf_vault_search_rows(ptr(q), ptr(bank), B, N, D, k, float(thresh), ptr(sims), ptr(idx),
+                                             ptr(disc), 1, ptr(text_emb), ptr(title_bank), ptr(tsim), ptr(ws),
+                                             ws.numel(), nblocks, stream_ptr()), "mmf_vault_search_rows")
+        return sims, idx, disc, tsim
+
     def fusion(self, x5):
         x5 = torch.as_tensor(x5, dtype=torch.float32).to(self.device).contiguous()
         B = x5.shape[0]

@@ -44,6 +44,8 @@ SIGNATURES = {
     "mmf_set_vault_normalized": (_I, [_P, _P, _I, _I]),
     "mmf_set_vault_titles": (_I, [_P, _P, _P, _I, _I, _P]),
     "mmf_vault_topk": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "mmf_vault_search_ws_bytes": (ctypes.c_int64, [_I, _I, _I]),
+    "mmf_vault_search_rows": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P, ctypes.c_int64, _I, _P]),
     "mmf_fusion": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "mmf_analyze_batch": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mmf_mixed_plan": (_I, [_P, _I, _P, _P]),

@@ -220,6 +220,29 @@ def load_vault(path: str):
     return np.ascontiguousarray(np.asarray(emb)), meta  # stored dtype kept (search renormalises in it)
 
 
+VAULT_DB_KEYS = ("article_ids", "text_contents", "image_paths", "image_embeddings", "text_embeddings", "metadata")
+
+
+def load_vault_db(path: str):
+    """The whole embeddings database that ``generate_embeddings_database`` pickles
+    (train_clip_detective.py:515-527): {article_ids, text_contents, image_paths, image_embeddings
+    [N, D], text_embeddings [N, D], metadata}, read with the restricted unpickler of ``load_vault``
+    (which keeps only the image rows and titles).  None when the file does not exist."""
+    if not os.path.exists(path):
+        return None
+    with open(path, "rb") as f:
+        d = _SafeUnpickler(io.BytesIO(f.read())).load()
+    missing = [k for k in VAULT_DB_KEYS if k not in d]
+    if missing:
+        raise ValueError(f"{path} is not an embeddings database: no {', '.join(missing)}")
+    db = {k: d[k] for k in VAULT_DB_KEYS}
+    for k in ("image_embeddings", "text_embeddings"):
+        db[k] = np.ascontiguousarray(np.asarray(db[k]))
+    for k in ("article_ids", "text_contents", "image_paths"):
+        db[k] = list(db[k])
+    return db
+
+
 def vault_unit_rows(emb) -> np.ndarray:
     """misinfo_forensics.py:443-445 as written: ``V / np.linalg.norm(V, axis=1, keepdims=True)`` in
     the vault's own dtype (a float16 vault renormalises in float16; a zero row becomes NaN, which

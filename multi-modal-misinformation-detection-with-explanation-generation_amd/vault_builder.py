@@ -148,3 +148,107 @@ def generate_embeddings_database(model_path: str = "clip_detective_best.pth",
         with open(output_file.replace(".pkl", "_summary.json"), "w", encoding="utf-8") as f:
             json.dump(summary, f, indent=2)
     return db
+
+
+# ---------------------------------------------------------------------------------------------
+# search_similar_articles (train_clip_detective.py:610-688): the database's second consumer
+# ---------------------------------------------------------------------------------------------
+QueryEncoder = Callable[[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]], Tuple]
+Searcher = Callable[[np.ndarray, np.ndarray, int], Tuple[np.ndarray, np.ndarray]]
+
+_DEVICE_TOP_K = 8   # mmf_vault_search_rows keeps its top-k in registers
+_BANKS: List[Tuple[Dict, Dict]] = []  # (db, {(mode, device): bank on the device}) of the last few databases
+
+
+def _device_bank(db: Dict, mode: str, engine) -> torch.Tensor:
+    """The mode's embedding table on the engine's device, uploaded once per ``db`` object (rows as
+    stored: the reference does not renormalise them, train_clip_detective.py:664)."""
+    for d, banks in _BANKS:
+        if d is db:
+            break
+    else:
+        banks = {}
+        _BANKS.append((db, banks))
+        del _BANKS[:-4]
+    key = (mode, str(engine.device))
+    if key not in banks:
+        rows = np.ascontiguousarray(db["text_embeddings" if mode == "text" else "image_embeddings"], dtype=np.float32)
+        banks[key] = torch.as_tensor(rows).to(engine.device).contiguous()
+    return banks[key]
+
+
+def engine_searcher(engine, db: Dict, mode: str) -> Searcher:
+    """The fused HIP search (Engine.search_rows) over the database's table of ``mode``."""
+    def search(q_unit, _rows, k):
+        if k > _DEVICE_TOP_K:
+            raise ValueError(f"the device search returns at most top_k = {_DEVICE_TOP_K} rows (got {k})")
+        bank = _device_bank(db, mode, engine)
+        sims, idx, _, _ = engine.search_rows(torch.as_tensor(q_unit).reshape(1, -1), bank, k=k)
+        return sims[0].cpu().numpy(), idx[0].cpu().numpy()
+    return search
+
+
+def search_similar_articles(query_text: Optional[str] = None, query_image_path: Optional[str] = None,
+                            embeddings_db_path: str = "guardian_embeddings.pkl", top_k: int = 5,
+                            search_mode: str = "text", *, processor=None, encode: Optional[QueryEncoder] = None,
+                            engine=None, search: Optional[Searcher] = None, db: Optional[Dict] = None,
+                            eos_token_id: int = 49407) -> List[Dict]:
+    """train_clip_detective.py:610-688 with the reference's signature, results and console output.
+
+    ``search_mode`` "text": ``query_text`` tokenised with truncation, embedded by the CLIP text tower
+    and renormalised, ranked against ``text_embeddings``; "image": the image at ``query_image_path``
+    through the CLIP geometry and the ViT, against ``image_embeddings``.  Database rows are used as
+    stored.  Anything else -- "multimodal" included, which the reference's docstring names and its
+    code rejects -- or a missing query raises ValueError.
+
+    ``encode(pixels | None, ids | None, mask | None) -> (image rows | None, text rows | None)`` and
+    ``search(q_unit [D], rows [N, D], k) -> (similarities [<= k], indices [<= k])`` default to the HIP
+    towers and the fused HIP search of ``engine`` (index -1 marks an empty slot of a short database);
+    ``db``: an already loaded database instead of ``embeddings_db_path``."""
+    print(f"\nSearching for similar articles (mode: {search_mode}, top_k: {top_k})...")
+    text_q = search_mode == "text" and bool(query_text)
+    image_q = search_mode == "image" and bool(query_image_path)
+    if not (text_q or image_q):
+        raise ValueError("Invalid search mode or missing query")
+    if db is None:
+        db = io_utils.load_vault_db(embeddings_db_path)
+        if db is None:
+            raise FileNotFoundError(embeddings_db_path)
+    if encode is None:
+        if engine is None:
+            raise RuntimeError("an engine with the CLIP towers loaded (engine=) or an encoder (encode=) is required")
+        encode = lambda px, ids, mask: (engine.clip_image(px) if px is not None else None,  # noqa: E731
+                                        engine.clip_text(ids, mask) if ids is not None else None)
+    if text_q:
+        if processor is None:
+            raise RuntimeError("a CLIP processor/tokenizer is required (pass processor=)")
+        seq = io_utils.tokenize_clip(processor, [query_text], truncation=True)[0][:77]
+        ids, mask = io_utils.pad_ids([seq], eos_token_id, 77)
+        q = encode(None, ids, mask)[1]
+        rows = db["text_embeddings"]
+    else:
+        px = io_utils.clip_pixels(io_utils.to_pil(query_image_path))[None]
+        q = encode(px, None, None)[0]
+        rows = db["image_embeddings"]
+    q = torch.as_tensor(q).detach().cpu().numpy().astype(np.float32).reshape(-1)
+    q = q / np.linalg.norm(q)
+    if search is None:
+        if engine is None:
+            raise RuntimeError("an engine (engine=) or a search function (search=) is required")
+        search = engine_searcher(engine, db, search_mode)
+    k = min(int(top_k), len(rows))
+    sims, idx = search(q, rows, k) if k > 0 else ((), ())
+    print(f"\nTop {top_k} similar articles:")
+    print("-" * 60)
+    results = []
+    for s, i in zip(np.asarray(sims).tolist(), np.asarray(idx).tolist()):
+        if i < 0:
+            continue
+        r = {"rank": len(results) + 1, "article_id": db["article_ids"][i], "similarity": float(s),
+             "text": db["text_contents"][i][:100] + "...", "image_path": db["image_paths"][i]}
+        results.append(r)
+        print(f"{r['rank']}. [{r['similarity']:.4f}] {r['article_id']}")
+        print(f"   {r['text']}")
+        print()
+    return results
+
