@@ -387,6 +387,106 @@ int mmf_effnet_stem_dw_f16(const uint8_t* img_u8, const float* x_f32_nchw, const
 int mmf_gap_classifier_f16(const void* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
                            int score_stride, int B, void* stream);
 
+/* Low-level ops exported for unit tests of the transformer towers' kernels (tests/test_gpu_transformer_kernels.py):
+ * norm.hip, precise.hip, the one-query attention and the split-K skinny GEMM.  No handle; every pointer
+ * is a device pointer; work is enqueued on `stream`.  "fp16" buffers are void*.  Null, shape and alignment
+ * checks run on the host; what a kernel does not support is MMF_EINVAL with nothing launched.
+ *
+ * Row kernels: one row of C in {512, 768} columns per wave; every row stride >= C and a multiple of 4.
+ *   layernorm: y = LN(x [+ add]) g + b -> y32 and / or y16.
+ *   add_ln_f32: s = x + y (y fp16); s32 = s, o32 = LN(s) (both nullable, row stride ldx, may alias x), o16 = LN(s).
+ *   add_ln_f16: the same on an fp16 stream: s16 = fp16(s) (nullable, may alias x16), o16 = LN of the stored s16.
+ *   add_ln_hilo: (hi, lo) = split(LN((hi + lo) + y)) in place, C = 768; lo NULL = hi alone; ovf (nullable,
+ *     needs L > 0): ovf[row / L] = 1 for a row with non-finite statistics.
+ *   hilo_rows: out [B][C] fp32 = hi[b * row_stride] + lo[b * row_stride] (lo nullable); C, row_stride % 4 == 0.
+ *   layernorm_split3: x = LN(x + add) in place [rows][768], s3 [rows][3 * 768] = [hi | lo | hi] of it
+ *     (hi = fp16(x), lo = fp16(x - hi); with_lo 0: the first third only). */
+int mmf_layernorm_f32(const float* x, int ldx, const float* add, int ldadd, const float* g, const float* b, float eps,
+                      float* y32, int ldy32, void* y16, int ldy16, int rows, int C, void* stream);
+int mmf_add_ln_f32(const float* x, int ldx, const void* y, int ldy, const float* g, const float* b, float eps,
+                   float* s32, float* o32, void* o16, int ldo, int rows, int C, void* stream);
+int mmf_add_ln_f16(const void* x16, int ldx, const void* y, int ldy, const float* g, const float* b, float eps,
+                   void* s16, void* o16, int ldo, int rows, int C, void* stream);
+int mmf_add_ln_hilo_f16(void* hi, void* lo, int ld, const void* y, int ldy, const float* g, const float* b, float eps,
+                        int rows, int C, int32_t* ovf, int L, void* stream);
+int mmf_hilo_rows_f32(const void* hi, const void* lo, int row_stride, float* out, int B, int C, void* stream);
+int mmf_layernorm_split3_f32(float* x, const float* add, const float* g, const float* b, float eps, void* s3,
+                             int with_lo, int rows, int C, void* stream);
+/* Embeddings.  RoBERTa: position id = pad_id + (number of non-pad ids up to and including t) for a non-pad
+ *   id, pad_id for a pad; row = LN(word[id] + type0 + pos[position id]) written as the split stream xb (hi) +
+ *   xlo (lo, nullable), or as fp32 x32 when that is non-NULL; ovf (nullable, [B]) as above.  H = 768, L <= 512;
+ *   every id must index word, pos needs pad_id + L + 1 rows.
+ * CLIP text: x = tok[id] + pos[t] stored as fp32 x or fp16 x16 (exactly one), then xb = LN(stored x) fp16, or,
+ *   with st (float2 [B * L]) non-NULL, st[row] = (mean, sum of squared deviations) of the stored row and xb is
+ *   not written.  H = 512.
+ * CLIP vision: row t of image b = pre-LN((t == 0 ? cls : patches[b * 49 + t - 1]) + pos[t]) stored to x / x16,
+ *   then xb / st as for the text embeddings; 50 rows of 768 per image.
+ * im2col: img uint8 [B][224][224][3] (8-byte aligned) -> A fp16 [B * 49][3072], column c * 1024 + ky * 32 + kx
+ *   of patch p = ((img / 255) - mean_c) / std_c with CLIP's constants. */
+int mmf_roberta_embed_f32(const int32_t* ids, const float* word, const float* pos, const float* type0, const float* g,
+                          const float* b, float eps, void* xlo, void* xb, float* x32, int32_t* ovf, int B, int L, int H,
+                          int pad_id, void* stream);
+int mmf_clip_text_embed_f32(const int32_t* ids, const float* tok, const float* pos, const float* g, const float* b,
+                            float eps, float* x, void* x16, void* xb, void* st, int B, int L, int H, void* stream);
+int mmf_clip_vision_assemble_f32(const float* patches, const float* cls, const float* pos, const float* pre_g,
+                                 const float* pre_b, const float* ln1_g, const float* ln1_b, float eps, float* x,
+                                 void* x16, void* xb, void* st, int B, void* stream);
+int mmf_clip_im2col_f16(const uint8_t* img, void* A, int B, void* stream);
+/* Pooling.  eos_index: out[b] = first t with ids[b][t] == eos_id (0 if none), or, with eos_id == 2, the first
+ *   position of the largest id; L <= 1024.  gather_ln: out16 / out32 [B][C] = LN(x[b * L + (idx ? idx[b] : 0)]),
+ *   C in {512, 768}.  gather_rows2: the same rows of a16 (fp16, nullable: o16 untouched) -> o16 and of a32 (fp32)
+ *   or a32h (fp16), exactly one, -> o32; C % 4 == 0.  l2norm: rows of x [B][C] scaled to unit length in place,
+ *   C % 64 == 0. */
+int mmf_eos_index_i32(const int32_t* ids, int32_t* out, int B, int L, int eos_id, void* stream);
+int mmf_gather_ln_f32(const float* x, const int32_t* idx, int L, const float* g, const float* b, float eps, void* out16,
+                      float* out32, int B, int C, void* stream);
+int mmf_gather_rows2(const void* a16, const float* a32, const void* a32h, const int32_t* idx, int L, int C, void* o16,
+                     float* o32, int B, void* stream);
+int mmf_l2norm_f32(float* x, int B, int C, void* stream);
+/* RoBERTa precise mode.  split3: out [rows][3C] = [hi | lo | hi] of x [rows][ldx] fp32 (with_lo 0: the first
+ *   third only); C, ldx % 4 == 0.  attention32: fp32 attention, head dim 64, over qkv fp32 [B * L][ld] (q at
+ *   h * 64, k at koff + h * 64, v at voff + h * 64; all % 4 == 0), key mask int32 [B][L] or NULL -> exactly one of
+ *   out fp32 [B * L][ldo] and out3 fp16 [B * L][3 * H * 64] = [hi | lo | hi] of the same values. */
+int mmf_split3_f32(const float* x, int ldx, void* out, int rows, int C, int with_lo, void* stream);
+int mmf_attention32_f32(const float* qkv, int ld, int koff, int voff, const int32_t* mask, float* out, int ldo,
+                        void* out3, int with_lo, int B, int L, int H, void* stream);
+/* One query per sequence (the compact last layer): q fp32 [B][ldq] (head h at h * 64) over the keys / values of
+ * qkv fp16 [B * L][ld] (columns koff + h * 64 / voff + h * 64); a key is excluded by mask 0 (int32 [B][L],
+ * nullable) or by lying past qpos[b] (nullable) -> out fp16 row b at out + b * ldo.  L <= 512; ldq % 4 == 0;
+ * ld, koff, voff % 8 == 0. */
+int mmf_attention_q1_f16(const float* q, int ldq, const void* qkv, int ld, int koff, int voff, const int32_t* mask,
+                         const int32_t* qpos, void* out, int ldo, int B, int L, int H, void* stream);
+/* mmf_gemm_f16 with the skinny-M path's split-K workspace: ws fp32 of ws_elems floats (nullable).  With M <= 512,
+ * N > 64 and S = mmf_gemm_splitk_factor(M, N, K, ldc) > 1, a workspace of >= S * M * N floats makes the GEMM
+ * run as S slices of K reduced in slice order; a smaller one (or process option gemm_splitk = 0) gives the
+ * unsplit kernel.  At most one of res32 (fp32 [M][N] ldc, may alias c32) and res16 (fp16 [M][N] ldc). */
+int mmf_gemm_splitk_factor(int M, int N, int K, int ldc);
+int mmf_gemm_f16_splitk(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res32,
+                        const void* res16, float* c32, void* c16, int ldc, int M, int N, int K, int act, float* ws,
+                        int64_t ws_elems, void* stream);
+/* The lazy-LayerNorm producer (gemm.hip epi 2): c16 = fp16(A @ W^T + bias + res16), res16 / c16 fp16 [M][ldc] (the
+ * same buffer: in place), and ln_out float2 [M][ceil(N / tn)] = per row and block of tn = mmf_gemm_ln_tn(M, N, K)
+ * consecutive columns the (mean, sum of squared deviations) of the stored values.  K % 64 == 0, K >= 192,
+ * ceil(N / tn) <= 8, else MMF_EINVAL. */
+int mmf_gemm_ln_tn(int M, int N, int K);
+int mmf_gemm_f16_ln_producer(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res16,
+                             void* c16, int ldc, void* ln_out, int M, int N, int K, void* stream);
+/* The lazy-LayerNorm consumer (gemm.hip epi 1): A fp16 [M][K] = raw stream rows s, W fp16 [N][K] = W diag(gamma),
+ * ln_u fp32 = its row sums, bias fp32 = b + W beta (both N + 256 entries: the tile's 256 columns are read whole),
+ * ln_in float2 [rows][P] = per row (mean, sum of squared deviations) over consecutive blocks of tn columns
+ * (rows padded to a multiple of 256; P * tn >= K, P <= 8) -> c16 = act(rstd (s W^T - mean u) + bias), act 0 / 1 /
+ * 2, with mean / rstd combined from the partials (Chan).  Padding may hold anything.  K % 64 == 0, K >= 192. */
+int mmf_gemm_f16_ln_consumer(const void* A, int lda, const void* W, int ldw, const float* bias, const void* ln_in,
+                             int P, int tn, const float* ln_u, float eps, void* c16, int ldc, int M, int N, int K,
+                             int act, void* stream);
+/* The QKV GEMM with the attention of its rows in the epilogue (gemm.hip epi 3): A fp16 [M][K] = sequences of 128
+ * rows, W fp16 [N][K] / bias [N] the fused QKV with rows interleaved per head ([q_h; k_h; v_h] = 192 rows for head
+ * h), amask int32 [M / 128][128] (1 keep) or NULL -> ctx fp16 [M][ldc], head h at columns 64 h: bit-identical to
+ * mmf_gemm_f16 on the same operands, de-interleaved, followed by mmf_attention_f16.  M % 128 == 0, N % 192 == 0,
+ * K % 64 == 0, K >= 192, ldc >= N / 3, else MMF_EINVAL. */
+int mmf_gemm_f16_attn(const void* A, int lda, const void* W, int ldw, const float* bias, const int32_t* amask, void* ctx,
+                      int ldc, int M, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

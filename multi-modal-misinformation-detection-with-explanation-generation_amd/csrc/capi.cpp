@@ -54,6 +54,8 @@ const OptName kOptNames[] = {
     {"mt_enqueue", &Options::mt_enqueue, "MMF_MT_ENQUEUE"}, {"last_q1", &Options::last_q1, "MMF_LAST_Q1"},
     {"after_text", &Options::after_text, "MMF_AFTER_TEXT"},
 };
+}  // namespace
+
 Options& process_options() {
   static Options o = [] {
     Options d;
@@ -65,6 +67,8 @@ Options& process_options() {
   }();
   return o;
 }
+
+namespace {
 
 const char* prof_kind_name(int k) {
   static const char* names[PK_COUNT - PK_ATTN] = {"attention", "layernorm", "embed+ln", "clip_im2col", "effnet_stem",

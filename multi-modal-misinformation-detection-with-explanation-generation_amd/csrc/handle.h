@@ -2,7 +2,8 @@
 // and profiling plumbing, and the launch wrappers the towers share.  The host side is one file per
 // seam: weights_host.cpp packs the weights, text_host.cpp / clip_host.cpp / effnet_host.cpp hold the
 // towers' launch sequences, resize_host.cpp the Pillow resize planner, capi.cpp the extern "C" surface (mixed_plan.cpp: its one
-// host-only function that needs neither the handle nor HIP).
+// host-only function that needs neither the handle nor HIP; test_host.cpp: the transformer kernels' test-only
+// entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,6 +171,9 @@ struct Options {
 // the options whose variants were measured slower and stayed off: gemm_ring, gemm_wide,
 // gemm_w4, dw_v2, dw_persist, ln_prod256, cu_split, fuse_expand32, qkv_attn_gm, splitk_fix, gemm_tq,
 // se_group, splitk_min_k, and pinned gemm_prio = 2 / dw_ct = 1; DESIGN.md §3 keeps each measurement.)
+
+// the process defaults (capi.cpp): what a handle starts from and what the handle-less test entry points use
+Options& process_options();
 
 inline void apply_options(const Options& o, GemmArgs* g) {
   g->force_cfg = o.gemm_config >= 0 ? o.gemm_config + 1 : 0;

@@ -121,6 +121,10 @@ __global__ __launch_bounds__(A32_Q) void attention32_kernel(const float* __restr
   if (qi >= L) return;
   const float inv = l == 0.f ? 0.f : 1.0f / l;  // (a non-finite sum propagates)
   if (out3) {  // the out-projection's operand row, split as split3_kernel does (fused: no fp32 ctx pass)
+    // the split is that of the rounded fp32 value o * inv (what the `out` form stores): contracting the product
+    // into the subtraction (fma(o, inv, -hi)) would make lo the split of the unrounded product instead, one
+    // fp16 ulp of lo away now and then
+#pragma clang fp contract(off)
     const int D = H * 64;
     f16_t* o3 = out3 + ((size_t)bi * L + qi) * 3 * D + h * 64;
 #pragma unroll

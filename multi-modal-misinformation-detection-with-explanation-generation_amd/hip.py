@@ -69,6 +69,30 @@ SIGNATURES = {
     "mmf_effnet_stem_f16": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "mmf_effnet_stem_dw_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mmf_gap_classifier_f16": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    # transformer-tower kernels on raw operands (csrc/test_host.cpp)
+    "mmf_layernorm_f32": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _P]),
+    "mmf_add_ln_f32": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
+    "mmf_add_ln_f16": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _P, _I, _I, _I, _P]),
+    "mmf_add_ln_hilo_f16": (_I, [_P, _P, _I, _P, _I, _P, _P, _F, _I, _I, _P, _I, _P]),
+    "mmf_hilo_rows_f32": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "mmf_layernorm_split3_f32": (_I, [_P, _P, _P, _P, _F, _P, _I, _I, _I, _P]),
+    "mmf_roberta_embed_f32": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_clip_text_embed_f32": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "mmf_clip_vision_assemble_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _P]),
+    "mmf_clip_im2col_f16": (_I, [_P, _P, _I, _P]),
+    "mmf_eos_index_i32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "mmf_gather_ln_f32": (_I, [_P, _P, _I, _P, _P, _F, _P, _P, _I, _I, _P]),
+    "mmf_gather_rows2": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
+    "mmf_l2norm_f32": (_I, [_P, _I, _I, _P]),
+    "mmf_split3_f32": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "mmf_attention32_f32": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "mmf_attention_q1_f16": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_gemm_splitk_factor": (_I, [_I, _I, _I, _I]),
+    "mmf_gemm_f16_splitk": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_int64, _P]),
+    "mmf_gemm_ln_tn": (_I, [_I, _I, _I]),
+    "mmf_gemm_f16_ln_producer": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "mmf_gemm_f16_ln_consumer": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
+    "mmf_gemm_f16_attn": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 _lib = None
