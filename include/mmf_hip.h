@@ -387,6 +387,37 @@ int mmf_effnet_stem_dw_f16(const uint8_t* img_u8, const float* x_f32_nchw, const
 int mmf_gap_classifier_f16(const void* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
                            int score_stride, int B, void* stream);
 
+/* Low-level ops exported for unit tests of the fp32 EfficientNet tower's kernels (option effnet_fp32;
+ * tests/test_gpu_effnet32_kernels.py).  No handle; every pointer is a device pointer; activations, weights
+ * and biases are fp32, activations NHWC; work is enqueued on `stream`.  Null, shape and alignment checks run on
+ * the host; anything unsupported is MMF_EINVAL with nothing launched.
+ *
+ * pw32_variant (host arithmetic only): the kernel a 1x1 convolution of M rows, N outputs, K inputs runs under
+ *   pw32_mfma mode `mfma` (0..5): returns 0 = the VALU kernel, 1 = pw32m<D>, 2 = pw32r<NF, D> over column tiles
+ *   of NC, and writes {D, NF, NC} to d_nf_nc (nullable; NF = 0 for kinds 0 and 1, D = 0 for kind 0).
+ * pw32: C [M][N] = act((A [M][K] .* ascale[m / rows_per_image][K]) W^T + bias) (+ res [M][N]); W [N][K], bias [N]
+ *   (required); ascale and res nullable; act 0 (none) or 3 (SiLU, by expf and a division); N % 4 == 0,
+ *   K % 4 == 0, rows_per_image >= 1 with ascale; every pointer 16-byte aligned.
+ * dw32: depthwise k x k (3 or 5, stride 1 or 2, zero padding (k - 1) / 2) + SiLU: in [B][H][W][C] -> out
+ *   [B][Ho][Wo][C], Ho = (H - 1) / stride + 1; w TAP-MAJOR [k*k][C], bias [C]; C % 4 == 0, B * H * W * C < 2^32.
+ * sum32: part [B][nchunks][C] = per channel the sum of x [B][HW][C] over the pixels [j HW / nchunks,
+ *   (j + 1) HW / nchunks) of chunk j, in the fixed order csrc/effnet_f32.hip documents; C % 16 == 0,
+ *   1 <= nchunks <= min(HW, 65535), HW <= 2^20, B <= 65535.
+ * gap32: global average pool + Linear(C, 2) + softmax: x [B][HW][C], w [2][C], b [2] -> logits [B][2] and / or
+ *   score[b * score_stride] = softmax(logits[b])[1] (either may be NULL, not both); score_stride >= 1.
+ * stem32: mmf_effnet_stem_f16's operands -> out fp32 [B][112][112][32]; from uint8 pixels the normalisation is
+ *   (u / 255 - mean) / std with two divisions, as torchvision evaluates it.  B <= 65535. */
+int mmf_pw32_variant(int M, int N, int K, int mfma, int32_t* d_nf_nc);
+int mmf_pw32_f32(const float* A, const float* W, const float* bias, const float* ascale, int rows_per_image,
+                 const float* res, float* C, int M, int N, int K, int act, int mfma, void* stream);
+int mmf_dw32_f32(const float* in, const float* w_tapmajor, const float* bias, float* out, int B, int H, int W, int C,
+                 int k, int stride, void* stream);
+int mmf_sum32_f32(const float* x, int B, int HW, int C, int nchunks, float* part, void* stream);
+int mmf_gap32_f32(const float* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
+                  int score_stride, int B, void* stream);
+int mmf_effnet_stem32_f32(const uint8_t* img_u8, const float* x_f32_nchw, const float* w, const float* bias,
+                          float* out_f32, int B, void* stream);
+
 /* Low-level ops exported for unit tests of the transformer towers' kernels (tests/test_gpu_transformer_kernels.py):
  * norm.hip, precise.hip, the one-query attention and the split-K skinny GEMM.  No handle; every pointer
  * is a device pointer; work is enqueued on `stream`.  "fp16" buffers are void*.  Null, shape and alignment

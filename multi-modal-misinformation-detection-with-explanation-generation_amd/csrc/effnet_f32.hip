@@ -447,11 +447,10 @@ __global__ __launch_bounds__(256) void gap32_kernel(const float* __restrict__ x,
 
 }  // namespace
 
-hipError_t launch_pw32(const float* A, const float* W, const float* bias, const float* ascale, int rows_per_image,
-                       const float* res, float* C, int M, int N, int K, int act, hipStream_t s, int mfma) {
-  if (M <= 0 || N <= 0 || K <= 0 || (N % 4) || (K % 4) || (ascale && rows_per_image <= 0) ||
-      (act != ACT_NONE && act != ACT_SILU))
-    return hipErrorInvalidValue;
+// Which kernel a pointwise launch runs, decided here alone (launch_pw32 and the host-only query
+// mmf_pw32_variant both call it; gemm_config / launch_gemm are the model).
+Pw32Variant pw32_variant(int M, int N, int K, int mfma) {
+  if (M <= 0 || N <= 0 || K <= 0 || (N % 4) || (K % 4)) return Pw32Variant{PW32_NONE, 0, 0, 0};
   // mode 5: mode 4 only where the whole-row grid has the parallelism for its long K (>= 1024 blocks,
   // or >= 512 at NF <= 5): the 14^2 / 7^2 projects with 112 / 192 columns keep pw32m's 64-column tiles
   const long rblocks = (M + QB - 1) / QB;
@@ -463,10 +462,29 @@ hipError_t launch_pw32(const float* A, const float* W, const float* bias, const 
     // this kernel they measured slower (B = 512 tower 11.39 -> 11.86 ms)
     const int ntl = (N + 255) / 256;
     const int NC = ((N + ntl - 1) / ntl + 15) / 16 * 16;
-    const int NF = NC / 16;
+    return Pw32Variant{PW32_ROWS, K >= 4 * QK ? 4 : 2, NC / 16, NC};
+  }
+  if (mfma) {
+    // mfma = 1: loads one chunk ahead (round 3); 2: three chunks ahead where K has >= 4 chunks and
+    // the grid leaves < 4 workgroups per CU (the 7^2-stage projects, K = 672 / 1152: 134 -> 107 and
+    // 199 -> 160 us per launch); launches with more workgroups hide the latency by occupancy and
+    // measured 1.3-1.7x SLOWER with the deeper prefetch (its 16 more VGPRs)
+    const long wgs = (long)((M + QB - 1) / QB) * ((N + QB - 1) / QB);
+    return Pw32Variant{PW32_MFMA, (mfma >= 2 && K >= 4 * QK && wgs < 4 * 256) ? 4 : 2, 0, QB};
+  }
+  return Pw32Variant{PW32_VALU, 0, 0, PB};
+}
+
+hipError_t launch_pw32(const float* A, const float* W, const float* bias, const float* ascale, int rows_per_image,
+                       const float* res, float* C, int M, int N, int K, int act, hipStream_t s, int mfma) {
+  const Pw32Variant v = pw32_variant(M, N, K, mfma);
+  if (v.kind == PW32_NONE || (ascale && rows_per_image <= 0) || (act != ACT_NONE && act != ACT_SILU))
+    return hipErrorInvalidValue;
+  if (v.kind == PW32_ROWS) {
+    const int NC = v.NC, NF = v.NF;
     const size_t lds = std::max((size_t)(2 * QB * QK + 2 * NF * 16 * QK), (size_t)QB * NC) * 4;
     const dim3 grid((M + QB - 1) / QB, (N + NC - 1) / NC);
-    const bool deep = K >= 4 * QK;
+    const bool deep = v.D == 4;
     switch (NF) {
 #define MMF_PW32R(F)                                                                                              \
   case F:                                                                                                         \
@@ -480,13 +498,9 @@ hipError_t launch_pw32(const float* A, const float* W, const float* bias, const 
     }
     return hipGetLastError();
   }
-  if (mfma) {
-    // mfma = 1: loads one chunk ahead (round 3); 2: three chunks ahead where K has >= 4 chunks and
-    // the grid leaves < 4 workgroups per CU (the 7^2-stage projects, K = 672 / 1152: 134 -> 107 and
-    // 199 -> 160 us per launch); launches with more workgroups hide the latency by occupancy and
-    // measured 1.3-1.7x SLOWER with the deeper prefetch (its 16 more VGPRs)
+  if (v.kind == PW32_MFMA) {
     const dim3 grid((M + QB - 1) / QB, (N + QB - 1) / QB);
-    if (mfma >= 2 && K >= 4 * QK && (long)grid.x * grid.y < 4 * 256)
+    if (v.D == 4)
       hipLaunchKernelGGL(pw32m_kernel<4>, grid, dim3(256), 0, s, A, W, bias, ascale, rows_per_image, res, C, M, N, K, act);
     else
       hipLaunchKernelGGL(pw32m_kernel<2>, grid, dim3(256), 0, s, A, W, bias, ascale, rows_per_image, res, C, M, N, K, act);

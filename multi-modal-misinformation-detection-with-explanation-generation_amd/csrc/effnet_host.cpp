@@ -262,3 +262,81 @@ int mmf_gap_classifier_f16(const void* x, int HW, int C, const float* w, const f
 }
 
 }  // extern "C"
+
+// ---- test-only entry points: the fp32 tower's kernels (effnet_f32.hip, stem_kernel<*, float>) on raw
+// device operands (include/mmf_hip.h; tests/test_gpu_effnet32_kernels.py).  The launchers check little
+// themselves: what their float4 accesses, 32-bit geometry and grid sizes assume is checked here.
+namespace {
+
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int mmf_pw32_variant(int M, int N, int K, int mfma, int32_t* d_nf_nc) {
+  const Pw32Variant v = pw32_variant(M, N, K, mfma);
+  if (mfma < 0 || mfma > 5 || v.kind == PW32_NONE)
+    return fail(MMF_EINVAL, "pw32_variant: unsupported (M=%d N=%d K=%d mfma=%d)", M, N, K, mfma);
+  if (d_nf_nc) {
+    d_nf_nc[0] = v.D;
+    d_nf_nc[1] = v.NF;
+    d_nf_nc[2] = v.NC;
+  }
+  return v.kind;
+}
+
+int mmf_pw32_f32(const float* A, const float* W, const float* bias, const float* ascale, int rows_per_image,
+                 const float* res, float* C, int M, int N, int K, int act, int mfma, void* stream) {
+  if (!A || !W || !bias || !C) return fail(MMF_EINVAL, "null argument");
+  if (mfma < 0 || mfma > 5) return fail(MMF_EINVAL, "pw32: mfma mode %d outside 0..5", mfma);
+  if (M <= 0 || N <= 0 || K <= 0 || (N % 4) || (K % 4) || (ascale && rows_per_image <= 0) ||
+      (act != 0 && act != 3 /* SiLU */))
+    return fail(MMF_EINVAL, "pw32: unsupported (M=%d N=%d K=%d act=%d rows_per_image=%d)", M, N, K, act,
+                rows_per_image);
+  if (!al16(A) || !al16(W) || !al16(bias) || !al16(ascale) || !al16(res) || !al16(C))
+    return fail(MMF_EINVAL, "pw32: operands must be 16-byte aligned");
+  return test_launch_rc(
+      launch_pw32(A, W, bias, ascale, rows_per_image, res, C, M, N, K, act, (hipStream_t)stream, mfma), "pw32");
+}
+
+int mmf_dw32_f32(const float* in, const float* w_tapmajor, const float* bias, float* out, int B, int H, int W, int C,
+                 int k, int stride, void* stream) {
+  if (!in || !w_tapmajor || !bias || !out) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) || (k != 3 && k != 5) || (stride != 1 && stride != 2))
+    return fail(MMF_EINVAL, "dw32: unsupported shape (B=%d H=%d W=%d C=%d k=%d stride=%d)", B, H, W, C, k, stride);
+  // the kernel's size_t offsets hold any buffer that exists; its grid is one thread per (image, output
+  // row, group of outputs, 4 channels), at most as many as input elements / 4, and must fit 2^32 threads
+  if ((double)B * H * W * C >= 4294967296.0) return fail(MMF_EINVAL, "dw32: B * H * W * C >= 2^32");
+  if (!al16(in) || !al16(w_tapmajor) || !al16(out)) return fail(MMF_EINVAL, "dw32: operands must be 16-byte aligned");
+  return test_launch_rc(launch_dw32(in, w_tapmajor, bias, out, B, H, W, C, k, stride, (hipStream_t)stream), "dw32");
+}
+
+int mmf_sum32_f32(const float* x, int B, int HW, int C, int nchunks, float* part, void* stream) {
+  if (!x || !part) return fail(MMF_EINVAL, "null argument");
+  // grid (C / 4 / L, ceil(nchunks L / 16), B) with L <= 16; pixel indices run to HW + 15 in an int
+  if (B <= 0 || B > 65535 || HW <= 0 || HW > (1 << 20) || C <= 0 || (C % 16) || nchunks < 1 || nchunks > HW ||
+      nchunks > 65535)
+    return fail(MMF_EINVAL, "sum32: unsupported shape (B=%d HW=%d C=%d nchunks=%d)", B, HW, C, nchunks);
+  if (!al16(x) || !al16(part)) return fail(MMF_EINVAL, "sum32: operands must be 16-byte aligned");
+  return test_launch_rc(launch_sum32(x, B, HW, C, nchunks, part, (hipStream_t)stream), "sum32");
+}
+
+int mmf_gap32_f32(const float* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
+                  int score_stride, int B, void* stream) {
+  if (!x || !w || !b || (!logits && !score)) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || B > (1 << 30) || HW <= 0 || C <= 0 || score_stride < 1)
+    return fail(MMF_EINVAL, "gap32: bad shape (B=%d HW=%d C=%d score_stride=%d)", B, HW, C, score_stride);
+  return test_launch_rc(launch_gap32(x, HW, C, w, b, logits, score, score_stride, B, (hipStream_t)stream), "gap32");
+}
+
+int mmf_effnet_stem32_f32(const uint8_t* img_u8, const float* x_f32_nchw, const float* w, const float* bias,
+                          float* out_f32, int B, void* stream) {
+  if (!w || !bias || !out_f32) return fail(MMF_EINVAL, "null argument");
+  if (!img_u8 == !x_f32_nchw) return fail(MMF_EINVAL, "stem32: exactly one of img_u8 / x_f32_nchw");
+  if (B <= 0 || B > 65535) return fail(MMF_EINVAL, "stem32: bad batch %d", B);
+  if (!al16(out_f32)) return fail(MMF_EINVAL, "stem32: out must be 16-byte aligned");
+  return test_launch_rc(launch_effnet_stem32(img_u8, x_f32_nchw, w, bias, out_f32, B, (hipStream_t)stream), "stem32");
+}
+
+}  // extern "C"

@@ -244,6 +244,13 @@ hipError_t launch_resize_pil(const uint8_t* src, const ResizeJob* jobs, int njob
 // fp32 EfficientNet tower (option effnet_fp32, effnet_f32.hip): NHWC fp32 activations
 hipError_t launch_effnet_stem32(const uint8_t* img, const float* x_nchw, const float* w, const float* bias,
                                 float* out, int B, hipStream_t s);
+// which kernel launch_pw32 runs for a shape and a pw32_mfma mode: pw32_kernel (VALU), pw32m_kernel<D>, or
+// pw32r_kernel<NF, D> over column tiles of NC; PW32_NONE = a shape no kernel takes (N, K % 4 != 0, ...)
+enum { PW32_NONE = -1, PW32_VALU = 0, PW32_MFMA = 1, PW32_ROWS = 2 };
+struct Pw32Variant {
+  int kind, D, NF, NC;
+};
+Pw32Variant pw32_variant(int M, int N, int K, int mfma);
 // C[M][N] = act((A .* ascale[m / rows_per_image]) W^T + bias) (+ res); W fp32 [N][K]; N, K % 4 == 0
 hipError_t launch_pw32(const float* A, const float* W, const float* bias, const float* ascale, int rows_per_image,
                        const float* res, float* C, int M, int N, int K, int act, hipStream_t s, int mfma = 1);

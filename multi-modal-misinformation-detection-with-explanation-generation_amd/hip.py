@@ -69,6 +69,13 @@ SIGNATURES = {
     "mmf_effnet_stem_f16": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "mmf_effnet_stem_dw_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mmf_gap_classifier_f16": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    # fp32 EfficientNet tower kernels on raw operands (csrc/effnet_host.cpp)
+    "mmf_pw32_variant": (_I, [_I, _I, _I, _I, _P]),
+    "mmf_pw32_f32": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "mmf_dw32_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "mmf_sum32_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "mmf_gap32_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "mmf_effnet_stem32_f32": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     # transformer-tower kernels on raw operands (csrc/test_host.cpp)
     "mmf_layernorm_f32": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _P]),
     "mmf_add_ln_f32": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
