@@ -203,6 +203,31 @@ int mmf_vault_topk(mmf_handle* h, const float* q_unit, int B, int k, float thres
 int mmf_fusion(mmf_handle* h, const float* scores5, int B, float* probs2, int32_t* verdict, float* confidence,
                int32_t* rule, void* stream);
 
+/* FusionJudge training (train_fusion_judge.py:213-233): ONE epoch -- forward in training mode
+ * (Linear(5,64)-ReLU-Dropout(p_drop)-Linear(64,32)-ReLU-Linear(32,2)), mean cross-entropy, backward
+ * and torch.optim.AdamW (decoupled weight decay, bias correction by global step) for each of the
+ * ceil(N / batch) minibatches -- in one launch.  No handle; asynchronous on `stream`.  All fp32;
+ * every reduction has a fixed order, so results are bit-reproducible and do not depend on how an
+ * epoch is split into launches.
+ *   scores5 fp32 [N][5], labels int32 [N] (0 / 1), perm int32 [N]: minibatch s takes positions
+ *     s*batch .. min(N, (s+1)*batch) - 1 of perm (the last may be short; its mean is over its own
+ *     rows).  A perm entry outside [0, N) is clamped, so no input makes the kernel read out of bounds.
+ *   keep uint64 [N] or NULL: keep[i] is the dropout mask of the row at POSITION i of the epoch order,
+ *     bit j set = hidden unit j kept and scaled by 1 / (1 - p_drop); NULL = no dropout, no scaling.
+ *   params, exp_avg, exp_avg_sq fp32 [MMF_FUSION_PARAMS], state-dict order, updated in place;
+ *     step0 = optimizer steps already taken (step s corrects its bias with step0 + s + 1).
+ *   step_loss fp32 [nsteps]: the minibatch's mean loss (train-mode logits, before its update);
+ *   step_correct int32 [nsteps]: rows with argmax(logits) == label (a tie is class 0, as torch.max);
+ *   grad_out fp32 [MMF_FUSION_PARAMS] or NULL: the gradient of the last minibatch.
+ * MMF_EINVAL with nothing launched: a NULL required pointer, N < 1, batch outside 1..256, p_drop
+ * outside [0, 1). */
+#define MMF_FUSION_PARAMS 2530  /* 0.weight[64][5], 0.bias[64], 3.weight[32][64], 3.bias[32], 5.weight[2][32], 5.bias[2] */
+int mmf_fusion_train_epoch(const float* scores5, const int32_t* labels, int N,
+                           const int32_t* perm, const uint64_t* keep, float p_drop, int batch,
+                           double lr, double beta1, double beta2, double eps, double weight_decay, int step0,
+                           float* params, float* exp_avg, float* exp_avg_sq,
+                           float* step_loss, int32_t* step_correct, float* grad_out, void* stream);
+
 /* The whole text+image analyze() path for B pairs (misinfo_forensics.py:767-927) with the ViT
  * computed once per pair.  Inputs device: RoBERTa ids/mask [B, Lr], CLIP ids/mask [B, Lc],
  * img_effnet uint8 [B,224,224,3], img_clip uint8 [B,224,224,3] (may equal img_effnet).

@@ -678,6 +678,21 @@ int mmf_fusion(mmf_handle* h, const float* x5, int B, float* probs, int32_t* ver
   return 0;
 }
 
+int mmf_fusion_train_epoch(const float* scores5, const int32_t* labels, int N, const int32_t* perm,
+                           const uint64_t* keep, float p_drop, int batch, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, int step0, float* params, float* exp_avg,
+                           float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* grad_out, void* stream) {
+  if (!scores5 || !labels || !perm || !params || !exp_avg || !exp_avg_sq || !step_loss || !step_correct)
+    return fail(MMF_EINVAL, "null argument");
+  if (N < 1 || batch < 1 || batch > 256 || !(p_drop >= 0.f && p_drop < 1.f))
+    return fail(MMF_EINVAL, "fusion_train_epoch: N=%d (>= 1) batch=%d (1..256) p_drop=%g ([0, 1))", N, batch,
+                (double)p_drop);
+  HIPCHK(launch_fusion_train_epoch(scores5, labels, N, perm, keep, p_drop, batch, lr, beta1, beta2, eps, weight_decay,
+                                   step0, params, exp_avg, exp_avg_sq, step_loss, step_correct, grad_out,
+                                   (hipStream_t)stream));
+  return 0;
+}
+
 int mmf_analyze_batch(mmf_handle* h, const int32_t* rob_ids, const int32_t* rob_mask, int Lr, const int32_t* clip_ids,
                       const int32_t* clip_mask, int Lc, const uint8_t* img_eff, const uint8_t* img_clip, int B,
                       float* scores5, float* text_sim, float* probs2, int32_t* verdict, float* conf, int32_t* rule,

@@ -145,6 +145,14 @@ hipError_t launch_text_heads(const float* x, int row_stride, const float* w1a, c
 hipError_t launch_fusion(const float* x5, const float* w0, const float* b0, const float* w3, const float* b3,
                          const float* w5, const float* b5, float* probs, int32_t* verdict, float* conf,
                          int32_t* rule, int B, hipStream_t s);
+// one epoch of FusionJudge training (forward, cross-entropy, backward, AdamW per minibatch) in one launch by one
+// workgroup (fusion_train.hip; include/mmf_hip.h mmf_fusion_train_epoch); hipErrorInvalidValue on a bad N / batch /
+// p_drop with nothing launched
+hipError_t launch_fusion_train_epoch(const float* scores5, const int32_t* labels, int N, const int32_t* perm,
+                                     const uint64_t* keep, float p_drop, int batch, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int step0, float* params,
+                                     float* exp_avg, float* exp_avg_sq, float* step_loss, int32_t* step_correct,
+                                     float* grad_out, hipStream_t s);
 // mmf_analyze_mixed's last kernel: per batch row, the row's compact tower results gathered through
 // row_map [B][3] (position of the row in the text / image / both lists; anything outside [0, n) is
 // absent), the CLIP cosine and the caption-title cosine of the "both" rows, the vault outputs scattered

@@ -530,6 +530,40 @@ class Engine:
               "mmf_fusion")
         return probs, verdict, conf, rule
 
+    FUSION_PARAMS = 2530  # MMF_FUSION_PARAMS: fusion_layer's parameters in state-dict order
+
+    def fusion_train_epoch(self, scores5, labels, perm, keep, p_drop: float, batch: int, lr: float, betas,
+                           eps: float, weight_decay: float, step0: int, params, exp_avg, exp_avg_sq,
+                           grad_out=None):
+        """One epoch of FusionJudge training in one launch (mmf_fusion_train_epoch): device tensors scores5
+        float32 [N, 5], labels int32 [N], perm int32 [N], keep int64 [N] (the uint64 masks' bits) or None;
+        params / exp_avg / exp_avg_sq float32 [2530], updated in place.  Returns (step_loss float32 [nsteps],
+        step_correct int32 [nsteps]) on the device; nothing is synchronised."""
+        N = int(labels.shape[0])
+        P = self.FUSION_PARAMS
+        for name, t, dt, n, optional in (("scores5", scores5, torch.float32, 5 * N, False),
+                                         ("labels", labels, torch.int32, N, False),
+                                         ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, N, True),
+                                         ("params", params, torch.float32, P, False),
+                                         ("exp_avg", exp_avg, torch.float32, P, False),
+                                         ("exp_avg_sq", exp_avg_sq, torch.float32, P, False),
+                                         ("grad_out", grad_out, torch.float32, P, True)):
+            if t is None and optional:
+                continue
+            if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.is_contiguous()
+                    and t.numel() == n):
+                raise ValueError(f"fusion_train_epoch: {name} must be a contiguous {dt} tensor of {n} elements on "
+                                 f"{self.device}")
+        nsteps = max(1, -(-N // max(1, int(batch))))
+        step_loss = self._f32(nsteps)
+        step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
+        check(self.lib.mmf_fusion_train_epoch(ptr(scores5), ptr(labels), N, ptr(perm), ptr(keep), float(p_drop),
+                                              int(batch), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                              float(weight_decay), int(step0), ptr(params), ptr(exp_avg),
+                                              ptr(exp_avg_sq), ptr(step_loss), ptr(step_correct), ptr(grad_out),
+                                              stream_ptr()), "mmf_fusion_train_epoch")
+        return step_loss, step_correct
+
     def analyze_batch(self, rob_ids, rob_mask, clip_ids, clip_mask, img, img_clip=None,
                       out: Optional[dict] = None) -> dict:
         """Text+image pairs through all five signals + fusion (misinfo_forensics.py:767-927)."""

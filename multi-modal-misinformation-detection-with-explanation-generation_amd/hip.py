@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmmf_hip.so")
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_D = ctypes.c_double
 SIGNATURES = {
     "mmf_create": (_I, [_I, ctypes.POINTER(_P)]),
     "mmf_destroy": (None, [_P]),
@@ -47,6 +48,7 @@ SIGNATURES = {
     "mmf_vault_search_ws_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "mmf_vault_search_rows": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P, ctypes.c_int64, _I, _P]),
     "mmf_fusion": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "mmf_fusion_train_epoch": (_I, [_P, _P, _I, _P, _P, _F, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmf_analyze_batch": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mmf_mixed_plan": (_I, [_P, _I, _P, _P]),
     "mmf_analyze_mixed": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
