@@ -115,22 +115,19 @@ bool vault_is_fused(const mmf_handle* h) {
 // the fused kernels (no similarity matrix), the similarity + top-k kernel pair over S[B][N], or, for
 // top_k > 8 on more than 16384 rows, the pair per 16384-row chunk and a final sort of the chunks' k each.
 // The workspaces were sized by ensure_sims (mmf_reserve, the vault setters, mmf_set_option).
-int vault_search(mmf_handle* h, const float* q, int B, int k, float thresh, float* sims, int32_t* idx, float* disc,
-                 int disc_stride, const float* temb, float* tsim, hipStream_t s) {
+int vault_search(mmf_handle* h, const float* q, int B, int k, const VaultOut& out, hipStream_t s) {
   Workspace& w = h->ws;
   const int N = h->vault_n, ref = h->opt.vault_ref;
   const char* unreserved = "vault search workspace not reserved (call mmf_reserve)";
   if (k <= 8 && vault_is_fused(h)) {
     if (!w.vs_ws) return fail(MMF_EINVAL, "%s", unreserved);
-    HIPCHK(launch_vault_search(q, h->vault, B, N, k, thresh, sims, idx, disc, disc_stride, temb, h->vault_title, tsim,
-                               w.vs_ws, 0, s));
+    HIPCHK(launch_vault_search(q, h->vault, B, N, k, out, w.vs_ws, 0, s));
     return 0;
   }
   if (k <= 8 || N <= kVaultChunk) {  // (the sort kernel of top_k > 8 holds at most kVaultChunk rows)
     if (w.s_cap_n < N) return fail(MMF_EINVAL, "%s", unreserved);
     HIPCHK(launch_vault_sims(q, h->vault, w.s_sims, B, N, 512, s, ref));
-    HIPCHK(launch_vault_topk(w.s_sims, B, N, k, thresh, sims, idx, disc, disc_stride, temb, h->vault_title, 512, tsim,
-                             s, ref));
+    HIPCHK(launch_vault_topk(w.s_sims, B, N, k, out, s, ref));
     return 0;
   }
   const int chunks = (N + kVaultChunk - 1) / kVaultChunk;
@@ -141,11 +138,12 @@ int vault_search(mmf_handle* h, const float* q, int B, int k, float thresh, floa
   for (int c = 0; c < chunks; ++c) {
     const int n = std::min(kVaultChunk, N - c * kVaultChunk);
     HIPCHK(launch_vault_sims(q, h->vault + (size_t)c * kVaultChunk * 512, w.s_sims, B, n, 512, s, ref));
-    HIPCHK(launch_vault_topk(w.s_sims, B, n, k, thresh, w.c_sims + (size_t)c * B * k, w.c_idx + (size_t)c * B * k,
-                             nullptr, 1, nullptr, nullptr, 512, nullptr, s, ref));
+    VaultOut part{};  // results only: the discrepancy and the caption similarity follow the final ranking
+    part.sims = w.c_sims + (size_t)c * B * k;
+    part.idx = w.c_idx + (size_t)c * B * k;
+    HIPCHK(launch_vault_topk(w.s_sims, B, n, k, part, s, ref));
   }
-  HIPCHK(launch_vault_sort_cand(w.c_sims, w.c_idx, chunks, kVaultChunk, B, k, thresh, sims, idx, disc, disc_stride, temb,
-                                h->vault_title, 512, tsim, s));
+  HIPCHK(launch_vault_sort_cand(w.c_sims, w.c_idx, chunks, kVaultChunk, B, k, out, s));
   return 0;
 }
 
@@ -156,7 +154,8 @@ int analyze_tail(mmf_handle* h, int B, float* scores5, float* text_sim, float* p
   HIPCHK(launch_rowdot(w.v_emb, w.t_emb, scores5 + 3, 5, B, 512, s));
   if (h->ready & RDY_VAULT) {
     ProfScope ps(h, s, PK_VAULT, 2.0 * B * h->vault_n * 512, (double)h->vault_n * 512 * 4 + (double)B * h->vault_n * 8);
-    CHK(vault_search(h, w.v_emb, B, 5, 0.85f, top_sims, top_idx, scores5 + 4, 5, w.t_emb, text_sim, s));
+    const VaultOut out{0.85f, top_sims, top_idx, scores5 + 4, 5, w.t_emb, h->vault_title, 512, text_sim};
+    CHK(vault_search(h, w.v_emb, B, 5, out, s));
   } else {
     HIPCHK(launch_fill_strided(scores5 + 4, 5, B, 0.f, s));
     if (text_sim) HIPCHK(hipMemsetAsync(text_sim, 0, (size_t)B * 4, s));
@@ -263,7 +262,11 @@ int mixed_tail(mmf_handle* h, const int32_t* row_map, int B, int nT, int nI, int
   const bool vault = nI > 0 && (h->ready & RDY_VAULT);
   if (vault) {
     ProfScope ps(h, s, PK_VAULT, 2.0 * nI * h->vault_n * 512, (double)h->vault_n * 512 * 4 + (double)nI * h->vault_n * 8);
-    CHK(vault_search(h, w.v_emb, nI, 5, 0.85f, w.m_sims, w.m_idx, w.m_disc, 1, nullptr, nullptr, s));
+    VaultOut out{};  // (the caption similarity is the finish kernel's: it knows which rows have a caption)
+    out.thresh = 0.85f;
+    out.sims = w.m_sims; out.idx = w.m_idx;
+    out.disc = w.m_disc; out.disc_stride = 1;
+    CHK(vault_search(h, w.v_emb, nI, 5, out, s));
   }
   MixedFinishArgs a{};
   a.row_map = row_map;
@@ -665,7 +668,8 @@ int mmf_vault_topk(mmf_handle* h, const float* q, int B, int k, float thresh, fl
   if (k < 1 || k > h->vault_n) return fail(MMF_EINVAL, "top_k must be in [1, N=%d]", h->vault_n);
   CHK(check_cap(h, B, 1, 1));
   HIPCHK(hipSetDevice(h->device));
-  return vault_search(h, q, B, k, thresh, sims, idx, disc, 1, temb, tsim, (hipStream_t)stream);
+  const VaultOut out{thresh, sims, idx, disc, 1, temb, h->vault_title, 512, tsim};
+  return vault_search(h, q, B, k, out, (hipStream_t)stream);
 }
 
 int mmf_fusion(mmf_handle* h, const float* x5, int B, float* probs, int32_t* verdict, float* conf, int32_t* rule,
@@ -950,8 +954,8 @@ int mmf_vault_search_rows(const float* q_unit, const float* bank_unit, int B, in
   if (ws_bytes < need)
     return fail(MMF_EINVAL, "mmf_vault_search_rows: workspace of %lld bytes, needs %lld", (long long)ws_bytes,
                 (long long)need);
-  hipError_t e = launch_vault_search(q_unit, bank_unit, B, N, k, thresh, sims, idx, disc, disc_stride, text_emb,
-                                     title_bank, text_sim, ws, nblocks, (hipStream_t)stream);
+  const VaultOut out{thresh, sims, idx, disc, disc_stride, text_emb, title_bank, 512, text_sim};
+  hipError_t e = launch_vault_search(q_unit, bank_unit, B, N, k, out, ws, nblocks, (hipStream_t)stream);
   if (e != hipSuccess) return fail(MMF_EIO, "vault search: %s", hipGetErrorString(e));
   return 0;
 }

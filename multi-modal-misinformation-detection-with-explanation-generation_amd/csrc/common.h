@@ -37,6 +37,25 @@ MMF_DEV float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// dot product of two rows of C floats by one wave (result on every lane): 8 columns per lane in flight,
+// then the ascending-i fmaf chain per lane and the wave sum.  The one definition behind every cosine of
+// misc.hip and vault.hip: a row's bits do not depend on which kernel computed it.
+MMF_DEV float wave_rowdot(const float* a, const float* c, int C, int lane) {
+  float s = 0.f;
+  for (int i0 = lane; i0 < C; i0 += 512) {
+    float ta[8], tc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = i0 + 64 * u;
+      ta[u] = i < C ? a[i] : 0.f;
+      tc[u] = i < C ? c[i] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (i0 + 64 * u < C) s = fmaf(ta[u], tc[u], s);
+  }
+  return wave_sum(s);
+}
 
 // activations (fp32).  Epilogue cost matters: a GEMM epilogue runs serially after the MFMA loop,
 // so IEEE erff / division (30-40 VALU ops) are replaced by short forms built on v_rcp_f32 /

@@ -162,7 +162,7 @@ struct Options {
   int diag_skip = 0;    // diagnostic: towers mmf_analyze_batch leaves out (bitmask; measurement only)
   int vault_ref = 0;    // diagnostic: vault similarities on the VALU kernel and top-k by full sort (the
                         // reference kernels the production ones are bit-identical to)
-  int vault_fused = 2;  // vault search without the similarity matrix (misc.hip vault_search_partial_kernel): 0 = the
+  int vault_fused = 2;  // vault search without the similarity matrix (vault.hip vault_search_partial_kernel): 0 = the
                         // two-kernel path, 1 = fused wherever top_k <= 8, 2 = fused iff the vault has > 16384 rows
   int after_text = 12;  // towers of the concurrent B > mt_enqueue step that start only once RoBERTa is done
                         // (bitmask as diag_skip: 2 EfficientNet, 4 CLIP text, 8 ViT)

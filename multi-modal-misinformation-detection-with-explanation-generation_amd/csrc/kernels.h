@@ -178,24 +178,32 @@ struct MixedFinishArgs {
 hipError_t launch_mixed_finish(const MixedFinishArgs& a, hipStream_t s);
 // cosine of unit rows: out[b*ostride] = dot(a[b], c[b])
 hipError_t launch_rowdot(const float* a, const float* c, float* out, int ostride, int B, int C, hipStream_t s);
-// vault: S[B][N] = Q[B][D] . V[N][D]^T (fp32)
+// vault (vault.hip): S[B][N] = Q[B][D] . V[N][D]^T (fp32)
 hipError_t launch_vault_sims(const float* q, const float* v, float* S, int B, int N, int D, hipStream_t s, int ref = 0);
-hipError_t launch_vault_topk(const float* S, int B, int N, int k, float thresh, float* sims, int32_t* idx,
-                             float* disc, int disc_stride, const float* text_emb, const float* title_emb, int D,
-                             float* text_sim, hipStream_t s, int ref = 0);
-// the same result without S (option vault_fused, mmf_vault_search_rows): D = 512, k in 1..8; ws holds
+// What a vault search writes for its B query rows (every pointer nullable), the same whichever kernel
+// path served it; passed to the kernels by value, as MixedFinishArgs.
+struct VaultOut {
+  float thresh;        // a hit: the top-1 similarity is above it (a NaN is not)
+  float* sims;         // [B][k] similarities, descending (NaN rows first); slots past N hold -inf
+  int32_t* idx;        // [B][k] their vault rows; slots past N hold -1
+  float* disc;         // disc[b * disc_stride] = the top-1 similarity of a hit, else 0
+  int disc_stride;
+  const float* temb;   // [B][D] unit caption embeddings  } both non-null: tsim[b] = the cosine of the
+  const float* title;  // [N][D] unit title embeddings    } caption and a hit's top-1 title, else 0
+  int D;
+  float* tsim;         // [B]
+};
+hipError_t launch_vault_topk(const float* S, int B, int N, int k, const VaultOut& out, hipStream_t s, int ref = 0);
+// the same result without S (option vault_fused, mmf_vault_search_rows): out.D = 512, k in 1..8; ws holds
 // vault_search_ws_bytes(B, k, nblocks) bytes of per-block candidates; nblocks 0 = vault_search_blocks' choice
 int vault_search_blocks(int B, int N, int nblocks);
 size_t vault_search_ws_bytes(int B, int k, int nblocks);
-hipError_t launch_vault_search(const float* q, const float* v, int B, int N, int k, float thresh, float* sims,
-                               int32_t* idx, float* disc, int disc_stride, const float* text_emb,
-                               const float* title_emb, float* text_sim, void* ws, int nblocks, hipStream_t s);
+hipError_t launch_vault_search(const float* q, const float* v, int B, int N, int k, const VaultOut& out, void* ws,
+                               int nblocks, hipStream_t s);
 // final ranking of [chunks][B][k] per-chunk top-k results (launch_vault_topk outputs with chunk-local
 // indices, chunk c = vault rows c * chunk_rows ..): chunks * k <= 16384
 hipError_t launch_vault_sort_cand(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
-                                  float thresh, float* sims, int32_t* idx, float* disc, int disc_stride,
-                                  const float* text_emb, const float* title_emb, int D, float* text_sim,
-                                  hipStream_t s);
+                                  const VaultOut& out, hipStream_t s);
 
 // EfficientNet-B0 pieces (NHWC fp16 activations)
 hipError_t launch_effnet_stem(const uint8_t* img, const float* w, const float* bias, f16_t* out, int B,

@@ -1,8 +1,7 @@
 // Small fp32 kernels at the ends of the path: the RoBERTa dual heads, the FusionJudge MLP with
-// verdict / explanation rule, cosine rows, and the Truth-Vault search (similarities + top-k).
+// verdict / explanation rule, cosine rows, mmf_analyze_mixed's finish and a strided fill (the
+// Truth-Vault search is vault.hip).
 // These are latency/L2-bound: they run in exact fp32 like the reference.
-#include <algorithm>
-
 #include "common.h"
 #include "kernels.h"
 
@@ -91,8 +90,9 @@ __global__ __launch_bounds__(1024) void text_heads_kernel(const float* x, int ro
 // fully exposed: a thread per row walked ~2.4k dependent FMAs, ~17 us).  Lane o computes hidden
 // unit o of Linear(5,64), lanes < 32 the units of Linear(64,32) from the wave's LDS row, lane 0
 // the two logits; every dot product keeps the ascending-index fmaf order of the scalar form.
-// The pieces below are shared by fusion_kernel / rowdot_kernel / vault_topk_kernel and by
-// mixed_finish_kernel (mmf_analyze_mixed), so a row's bits do not depend on which of them computed it.
+// The pieces below are shared by fusion_kernel and mixed_finish_kernel (mmf_analyze_mixed), and
+// common.h's wave_rowdot by rowdot_kernel, mixed_finish_kernel and the vault kernels (vault.hip), so a
+// row's bits do not depend on which of them computed it.
 //
 // The block's LDS image of the fusion layer (4 waves = 4 rows per block)
 struct FusionLds {
@@ -161,25 +161,6 @@ MMF_DEV void write_verdict(int row, float p0, float p1, const float* x, float* p
   if (rule) rule[row] = explanation_rule(x);
 }
 
-// dot product of two rows of C floats by one wave (result on every lane): 8 columns per lane in flight,
-// then the ascending-i fmaf chain per lane and the wave sum
-MMF_DEV float wave_rowdot(const float* a, const float* c, int C, int lane) {
-  float s = 0.f;
-  for (int i0 = lane; i0 < C; i0 += 512) {
-    float ta[8], tc[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + 64 * u;
-      ta[u] = i < C ? a[i] : 0.f;
-      tc[u] = i < C ? c[i] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (i0 + 64 * u < C) s = fmaf(ta[u], tc[u], s);
-  }
-  return wave_sum(s);
-}
-
 __global__ __launch_bounds__(256) void fusion_kernel(const float* x5, const float* w0, const float* b0,
                                                      const float* w3, const float* b3, const float* w5,
                                                      const float* b5, float* probs, int32_t* verdict, float* conf,
@@ -239,7 +220,7 @@ __global__ __launch_bounds__(256) void mixed_finish_kernel(MixedFinishArgs a) {
   // wave-uniform branches: the whole wave works on one row
   if (has_c) x[3] = wave_rowdot(a.v_emb + (size_t)ii * 512, a.t_emb + (size_t)ci * 512, 512, lane);
   float tsim = 0.f;
-  // vault_topk_kernel's hit: top-1 above the threshold (a NaN or an empty slot is not)
+  // vault.hip's hit (vault_top1): top-1 above the threshold (a NaN or an empty slot is not)
   if (has_c && vault && a.title && top1 > a.thresh && top1_idx >= 0)
     tsim = wave_rowdot(a.t_emb + (size_t)ci * 512, a.title + (size_t)top1_idx * 512, 512, lane);
   if (live && lane < 5) {
@@ -261,551 +242,6 @@ __global__ __launch_bounds__(256) void mixed_finish_kernel(MixedFinishArgs a) {
     p1 = fake;
   }
   write_verdict(row, p0, p1, x, a.probs, a.verdict, a.conf, a.rule);
-}
-
-// S[B][N] = Q[B][D] . V[N][D]^T, fp32 (misinfo_forensics.py:446).  Tile 16 queries x 64 rows,
-// 64-deep K chunks staged through LDS with 16-B loads; the next chunk's loads (clamped rows,
-// no divergent region) are in flight while the current one is consumed.  Every output is one
-// fp32 FMA chain over k = 0 .. D-1 in order.  D % 64 == 0 (host-checked).
-__global__ __launch_bounds__(256) void vault_sims_kernel(const float* q, const float* v, float* S, int B, int N,
-                                                         int D) {
-  constexpr int KC = 64, LD = KC + 4;  // row stride 68 floats: 16-B aligned, rows 4 banks apart
-  __shared__ __attribute__((aligned(16))) float qs[16 * LD];
-  __shared__ __attribute__((aligned(16))) float vs[64 * LD];
-  const int tid = threadIdx.x, tq = tid >> 4, tv = tid & 15;
-  const int q0 = blockIdx.y * 16, v0 = blockIdx.x * 64;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  // this thread's chunk pieces: one float4 of Q (row tid / 16, col 4 (tid % 16)), four of V
-  const int qr = tid >> 4, qc = (tid & 15) * 4;
-  const float* qp = q + (size_t)min(q0 + qr, B - 1) * D + qc;
-  const float* vp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) vp[i] = v + (size_t)min(v0 + qr + 16 * i, N - 1) * D + qc;
-  float4 rq, rv[4];
-  auto load = [&](int k0) {
-    rq = *reinterpret_cast<const float4*>(qp + k0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rv[i] = *reinterpret_cast<const float4*>(vp[i] + k0);
-  };
-  load(0);
-  for (int k0 = 0; k0 < D; k0 += KC) {
-    *reinterpret_cast<float4*>(qs + qr * LD + qc) = rq;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(vs + (qr + 16 * i) * LD + qc) = rv[i];
-    __syncthreads();
-    if (k0 + KC < D) load(k0 + KC);
-#pragma unroll 16
-    for (int k = 0; k < KC; ++k) {
-      const float a = qs[tq * LD + k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = fmaf(a, vs[(tv + 16 * j) * LD + k], acc[j]);
-    }
-    __syncthreads();
-  }
-  if (q0 + tq < B) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (v0 + tv + 16 * j < N) S[(size_t)(q0 + tq) * N + v0 + tv + 16 * j] = acc[j];
-  }
-}
-
-// The same similarities on the fp32-input MFMA (v_mfma_f32_16x16x4_f32: bit-for-bit a k-ordered fmaf
-// chain, as effnet_f32.hip's pw32m): BIT-IDENTICAL to vault_sims_kernel (every output the chain over
-// k = 0 .. D-1 in order from 0) at the MFMA rate -- the launch sits on the step's serial tail.  Block
-// = 64 vault rows x 16 queries, wave w = vault rows 16 w .. 16 w + 15; K in 16-deep chunks staged
-// through LDS k-transposed ([row][g][s] = X[row][4 s + g]: a lane of group g reads its four steps'
-// operands k = g, 4 + g, 8 + g, 12 + g with one ds_read_b128; step s covers k = 4 s .. 4 s + 3 in
-// lane-group order), the next chunk's loads in flight under the current one's MFMAs.  Vault rows are
-// the MFMA's A operand, so each lane ends with 4 consecutive vault rows of one query: 16-B stores.
-__device__ __forceinline__ int vq_off(int row, int g) { return row * 16 + ((g ^ (((row >> 3) & 1) << 1)) << 2); }
-
-// CH 16-deep chunks per LDS stage (one barrier per 16 CH of K; D % (16 CH) == 0, host-checked): the
-// same chunk images and MFMA order as CH = 1, so the same ascending-k chains
-template <int CH>
-__global__ __launch_bounds__(256) void vault_sims_mfma_kernel(const float* __restrict__ q, const float* __restrict__ v,
-                                                              float* __restrict__ S, int B, int N, int D) {
-  __shared__ __attribute__((aligned(16))) float qs[2][CH][16 * 16];
-  __shared__ __attribute__((aligned(16))) float vs[2][CH][64 * 16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-  const int n0 = blockIdx.x * 64, b0 = blockIdx.y * 16;
-  // loaders: V chunk 64 x 16 = one float4 per thread (row lr, k quad lc); Q chunk 16 x 16 = threads 0-63
-  const int lr = tid >> 2, lc = tid & 3;
-  const float* vp = v + (size_t)min(n0 + lr, N - 1) * D + lc * 4;  // clamped rows: loaded, never stored
-  const float* qp = q + (size_t)min(b0 + (lr & 15), B - 1) * D + lc * 4;
-  float4 rv[CH], rq[CH];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int h = 0; h < CH; ++h) {
-      rv[h] = *reinterpret_cast<const float4*>(vp + k0 + 16 * h);
-      rq[h] = *reinterpret_cast<const float4*>(qp + k0 + 16 * h);
-    }
-  };
-  auto lstore = [&](int buf) {  // k = 4 lc + e -> [row][g = e][s = lc]
-#pragma unroll
-    for (int h = 0; h < CH; ++h) {
-      const float av[4] = {rv[h].x, rv[h].y, rv[h].z, rv[h].w}, bv[4] = {rq[h].x, rq[h].y, rq[h].z, rq[h].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) vs[buf][h][vq_off(lr, e) + lc] = av[e];
-      if (tid < 64) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) qs[buf][h][vq_off(lr, e) + lc] = bv[e];
-      }
-    }
-  };
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nst = D / (16 * CH);
-  gload(0);
-  lstore(0);
-  __syncthreads();
-  for (int c = 0; c < nst; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nst) gload((c + 1) * 16 * CH);
-#pragma unroll
-    for (int h = 0; h < CH; ++h) {
-      const float4 wf = *reinterpret_cast<const float4*>(&vs[buf][h][vq_off(wave * 16 + fr, fg)]);
-      const float4 xf = *reinterpret_cast<const float4*>(&qs[buf][h][vq_off(fr, fg)]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf.x, xf.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf.y, xf.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf.z, xf.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf.w, xf.w, acc, 0, 0, 0);
-    }
-    if (c + 1 < nst) lstore(buf ^ 1);
-    __syncthreads();
-  }
-  // lane: S[query b0 + fr][vault rows n .. n + 3], n = n0 + 16 wave + 4 fg
-  const int b = b0 + fr, n = n0 + wave * 16 + fg * 4;
-  if (b < B) {
-    float* dst = S + (size_t)b * N + n;
-    if (n + 3 < N && ((N & 3) == 0)) {
-      *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < N) dst[r] = acc[r];
-    }
-  }
-}
-
-// Ranking of the reference's np.argsort(sims)[-k:][::-1] (misinfo_forensics.py:449): value
-// descending; numpy sorts NaN (a zero-norm vault row: 0/0 in the renormalisation, :443-445) after
-// every number, so the reversed tail puts NaN rows FIRST.  The scans rank by a key: the similarity,
-// with NaN mapped to +inf (a cosine of unit rows is never +inf) and mapped back on output; empty
-// slots hold -inf with index -1.  Exact ties: numpy's default sort is not stable (its tie order is
-// data- and platform-dependent); ties are ordered here by descending index = what a
-// stable argsort would give.
-MMF_DEV float rank_key(float v) { return v != v ? INFINITY : v; }
-MMF_DEV float unkey(float k) { return k == INFINITY ? NAN : k; }
-MMF_DEV bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia > ib); }
-
-// One 256-thread block per query row: each wave keeps per-lane top-K lists over its share of the
-// columns (columns w * 64 + lane + 256 i, 8 loads in flight per lane), reduces them to the wave's
-// top-K, and wave 0 merges the four waves' 4K candidates.  `better` is a strict total order (value,
-// then index), so the K selected (value, index) pairs do not depend on how the columns were split.
-template <int K>
-__global__ __launch_bounds__(256) void vault_topk_kernel(const float* S, int B, int N, float thresh, float* sims,
-                                                         int32_t* idx, float* disc, int disc_stride,
-                                                         const float* temb, const float* title, int D,
-                                                         float* tsim) {
-  static_assert(4 * K <= 64, "wave 0 holds the 4K candidates one per lane");
-  __shared__ float cv[4 * K];
-  __shared__ int ci[4 * K];
-  const int row = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (row >= B) return;  // (uniform per block)
-  float tv[K];
-  int ti[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -INFINITY; ti[i] = -1; }
-  const float* s = S + (size_t)row * N;
-  for (int j0 = wave * 64 + lane; j0 < N; j0 += 256 * 8) {
-    float vv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) vv[u] = (j0 + 256 * u < N) ? rank_key(s[j0 + 256 * u]) : -INFINITY;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const float v = vv[u];
-      const int vi = j0 + 256 * u;
-      if (vi < N && better(v, vi, tv[K - 1], ti[K - 1])) {
-        tv[K - 1] = v; ti[K - 1] = vi;
-#pragma unroll
-        for (int i = K - 1; i > 0; --i) {
-          if (better(tv[i], ti[i], tv[i - 1], ti[i - 1])) {
-            const float a = tv[i]; tv[i] = tv[i - 1]; tv[i - 1] = a;
-            const int b = ti[i]; ti[i] = ti[i - 1]; ti[i - 1] = b;
-          }
-        }
-      }
-    }
-  }
-  // the wave's top K: K rounds of a wave arg-max over the lists' heads, the winning lane pops
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    float bv = tv[0];
-    int bi = ti[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { cv[wave * K + t] = bv; ci[wave * K + t] = bi; }
-    if (ti[0] == bi) {
-#pragma unroll
-      for (int i = 0; i < K - 1; ++i) { tv[i] = tv[i + 1]; ti[i] = ti[i + 1]; }
-      tv[K - 1] = -INFINITY; ti[K - 1] = -1;
-    }
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  // merge: lane l < 4K holds candidate l
-  float mv = lane < 4 * K ? cv[lane] : -INFINITY;
-  int mi = lane < 4 * K ? ci[lane] : -1;
-  float outv[K];
-  int outi[K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    float bv = mv;
-    int bi = mi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    outv[t] = bv; outi[t] = bi;
-    if (mi == bi) { mv = -INFINITY; mi = -1; }
-  }
-  const bool hit = outv[0] > thresh && outv[0] != INFINITY;  // NaN > thresh is false
-  if (lane == 0) {
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      if (sims) sims[(size_t)row * K + t] = unkey(outv[t]);
-      if (idx) idx[(size_t)row * K + t] = outi[t];
-    }
-    if (disc) disc[(size_t)row * disc_stride] = hit ? outv[0] : 0.f;
-  }
-  if (tsim) {
-    float d = 0.f;
-    if (hit && temb && title) d = wave_rowdot(temb + (size_t)row * D, title + (size_t)outi[0] * D, D, lane);
-    if (lane == 0) tsim[row] = d;
-  }
-}
-
-// top-k for k > 8 (search_vault's top_k is a free parameter): one 1024-thread block per query
-// row sorts all N similarities (padded to P, a power of two) in LDS with a bitonic network under
-// the same `better` order, then writes the first k.  N <= P <= 16384 (128 KB of LDS).
-template <int P>
-__global__ __launch_bounds__(1024) void vault_sort_topk_kernel(const float* S, int B, int N, int k, float thresh,
-                                                               float* sims, int32_t* idx, float* disc,
-                                                               int disc_stride, const float* temb,
-                                                               const float* title, int D, float* tsim) {
-  __shared__ float key[P];
-  __shared__ int id[P];
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const float* s = S + (size_t)row * N;
-  for (int i = tid; i < P; i += 1024) {
-    key[i] = i < N ? rank_key(s[i]) : -INFINITY;
-    id[i] = i < N ? i : -1;
-  }
-  __syncthreads();
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P / 2; i += 1024) {
-        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
-        const bool desc = (lo & size) == 0;  // descending segments; the final pass is all-descending
-        const float a = key[lo], b = key[hi];
-        const int ia = id[lo], ib = id[hi];
-        if (desc ? better(b, ib, a, ia) : better(a, ia, b, ib)) {
-          key[lo] = b; key[hi] = a;
-          id[lo] = ib; id[hi] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const bool hit = key[0] > thresh && key[0] != INFINITY;
-  for (int t = tid; t < k; t += 1024) {
-    if (sims) sims[(size_t)row * k + t] = unkey(key[t]);
-    if (idx) idx[(size_t)row * k + t] = id[t];
-  }
-  if (tid == 0 && disc) disc[(size_t)row * disc_stride] = hit ? key[0] : 0.f;  // (a hit is finite)
-  if (tsim && tid < 64) {
-    float d = 0.f;
-    if (hit && temb && title) {
-      for (int c = tid; c < D; c += 64) d = fmaf(temb[(size_t)row * D + c], title[(size_t)id[0] * D + c], d);
-      d = wave_sum(d);
-    }
-    if (tid == 0) tsim[row] = d;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Fused similarity + top-k (mmf_vault_search_rows, option vault_fused): the result of
-// vault_sims_mfma_kernel + vault_topk_kernel without S[B][N].  Every similarity is the same chain
-// (v_mfma_f32_16x16x4_f32 over k = 0 .. 511 in order from 0, vault rows = A operand) and the ranking
-// the same `better` order, so the selected (value, index) pairs are bit-identical.
-//
-// Partial kernel: grid (nblocks, ceil(B / 64)).  A block keeps its 64 queries in LDS for the whole
-// kernel (four 16-query groups x 32 chunk images in vault_sims_mfma_kernel's k-transposed layout,
-// 128 KB; rows past B are zero) and walks a contiguous range of 64-row vault tiles; wave w owns rows
-// 16 w .. 16 w + 15 of each tile.  A wave fetches its 16 x 512 slice once per tile with 16-B loads
-// (the next tile's loads are in flight while this one is consumed -- they are the only global loads
-// of the loop, so nothing queues behind them), turns it into the MFMA's A layout through a 4 KB
-// wave-private LDS scratch and holds it in 128 registers; the query groups then stream past it two
-// at a time, one accumulator each, so the 40-cycle dependent MFMA latency hides behind the other
-// chain's 32-cycle issue.  The loop has no block barrier.  Each lane keeps a register top-K per query
-// group (its query 16 j + lane % 16, the rows it saw); at the end the 16 lists of a query (4 waves x
-// 4 lane groups) meet in LDS and one thread per query writes the block's K candidates.
-constexpr int kVsQ = 64;        // queries per block
-constexpr int kVsAuto = 256;    // blocks of the automatic grid (one per CU: the block owns the LDS)
-
-template <int K>
-MMF_DEV void topk_insert(float (&tv)[K], int (&ti)[K], float v, int vi) {
-  if (better(v, vi, tv[K - 1], ti[K - 1])) {
-    tv[K - 1] = v; ti[K - 1] = vi;
-#pragma unroll
-    for (int i = K - 1; i > 0; --i) {
-      if (better(tv[i], ti[i], tv[i - 1], ti[i - 1])) {
-        const float a = tv[i]; tv[i] = tv[i - 1]; tv[i - 1] = a;
-        const int b = ti[i]; ti[i] = ti[i - 1]; ti[i - 1] = b;
-      }
-    }
-  }
-}
-
-// the wave's top K of its lanes' sorted lists (K rounds of a wave arg-max over the heads, the winning
-// lane pops), valid on every lane
-template <int K>
-MMF_DEV void wave_topk(float (&tv)[K], int (&ti)[K], float (&outv)[K], int (&outi)[K]) {
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    float bv = tv[0];
-    int bi = ti[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    outv[t] = bv; outi[t] = bi;
-    if (ti[0] == bi) {
-#pragma unroll
-      for (int i = 0; i < K - 1; ++i) { tv[i] = tv[i + 1]; ti[i] = ti[i + 1]; }
-      tv[K - 1] = -INFINITY; ti[K - 1] = -1;
-    }
-  }
-}
-
-template <int K>
-__global__ __launch_bounds__(256) void vault_search_partial_kernel(const float* __restrict__ q,
-                                                                   const float* __restrict__ v, int B, int N,
-                                                                   float* __restrict__ cv, int* __restrict__ ci) {
-  __shared__ __attribute__((aligned(16))) float qs[4][32][16 * 16];  // [group][chunk][vq_off image]
-  __shared__ __attribute__((aligned(16))) float ts[4][4][16 * 16];   // per wave: four chunk images
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
-  const int tiles = (N + 63) / 64, nb = gridDim.x;
-  const int t0 = (int)((long long)blockIdx.x * tiles / nb), t1 = (int)((long long)(blockIdx.x + 1) * tiles / nb);
-  const int q0 = blockIdx.y * kVsQ;
-  const int ng = min(4, (B - q0 + 15) / 16);  // query groups of this block (>= 1)
-  // the block's queries -> LDS: thread = (row tid / 4, k quad tid % 4) of a 16 x 16 chunk, as the
-  // similarity kernel's loader; wave j stages group j
-  {
-    const int lr = lane >> 2, lc = lane & 3, b = q0 + wave * 16 + lr;
-    const float* qp = q + (size_t)min(b, B - 1) * 512 + lc * 4;
-#pragma unroll 4
-    for (int h = 0; h < 32; ++h) {
-      float4 x = *reinterpret_cast<const float4*>(qp + 16 * h);
-      if (b >= B) x = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) qs[wave][h][vq_off(lr, e) + lc] = xv[e];
-    }
-  }
-  __syncthreads();
-  float tv[4][K];
-  int ti[4][K];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < K; ++i) { tv[j][i] = -INFINITY; ti[j][i] = -1; }
-  // the wave's slice of a tile: lane = (row lane / 4, k quad lane % 4), 32 chunks
-  const int lr = lane >> 2, lc = lane & 3;
-  float4 rv[32];
-  auto gload = [&](int t) {
-    const float* vp = v + (size_t)min(t * 64 + wave * 16 + lr, N - 1) * 512 + lc * 4;  // clamped: loaded, never ranked
-#pragma unroll
-    for (int h = 0; h < 32; ++h) rv[h] = *reinterpret_cast<const float4*>(vp + 16 * h);
-  };
-  if (t0 < t1) gload(t0);
-  for (int t = t0; t < t1; ++t) {
-    // A layout through the wave's scratch, four chunks a round (the LDS serves a wave's accesses in
-    // order; the wave barriers keep the compiler from moving them across each other)
-    float4 a[32];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 x = rv[4 * r + c];
-        const float xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ts[wave][c][vq_off(lr, e) + lc] = xv[e];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-      for (int c = 0; c < 4; ++c) a[4 * r + c] = *reinterpret_cast<const float4*>(&ts[wave][c][vq_off(fr, fg)]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    if (t + 1 < t1) gload(t + 1);
-    const int n = t * 64 + wave * 16 + fg * 4;  // lane: rows n .. n + 3 of query 16 j + fr
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      if (2 * p >= ng) break;  // (uniform per block)
-      f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int h = 0; h < 32; ++h) {
-        const float4 x0 = *reinterpret_cast<const float4*>(&qs[2 * p][h][vq_off(fr, fg)]);
-        const float4 x1 = *reinterpret_cast<const float4*>(&qs[2 * p + 1][h][vq_off(fr, fg)]);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].x, x0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].x, x1.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].y, x0.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].y, x1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].z, x0.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].z, x1.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].w, x0.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h].w, x1.w, acc1, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < N) topk_insert<K>(tv[2 * p], ti[2 * p], rank_key(acc0[r]), n + r);
-      if (2 * p + 1 < ng) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (n + r < N) topk_insert<K>(tv[2 * p + 1], ti[2 * p + 1], rank_key(acc1[r]), n + r);
-      }
-    }
-  }
-  // the 16 lists of a query -> LDS (over the query images, which every wave is done with), one
-  // thread per query selects the block's K
-  __syncthreads();
-  float* lv = &qs[0][0][0];                                  // [source 16][K][query 64]
-  int* li = reinterpret_cast<int*>(&qs[0][0][0]) + 16 * K * kVsQ;
-  const int src = wave * 4 + fg;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      lv[(src * K + i) * kVsQ + 16 * j + fr] = tv[j][i];
-      li[(src * K + i) * kVsQ + 16 * j + fr] = ti[j][i];
-    }
-  __syncthreads();
-  if (tid < kVsQ && q0 + tid < B) {
-    float bv[K];
-    int bi[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) { bv[i] = -INFINITY; bi[i] = -1; }
-    for (int c = 0; c < 16 * K; ++c) {
-      const int vi = li[c * kVsQ + tid];
-      if (vi >= 0) topk_insert<K>(bv, bi, lv[c * kVsQ + tid], vi);
-    }
-    const size_t o = ((size_t)blockIdx.x * B + q0 + tid) * K;
-#pragma unroll
-    for (int i = 0; i < K; ++i) { cv[o + i] = bv[i]; ci[o + i] = bi[i]; }
-  }
-}
-
-// Merge kernel: one wave per query ranks the nblocks * K candidates (keys, as the partial kernel
-// left them) and runs vault_topk_kernel's epilogue.
-template <int K>
-__global__ __launch_bounds__(64) void vault_search_merge_kernel(const float* __restrict__ cv, const int* __restrict__ ci,
-                                                                int nblocks, int B, float thresh, float* sims,
-                                                                int32_t* idx, float* disc, int disc_stride,
-                                                                const float* temb, const float* title, int D,
-                                                                float* tsim) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  float tv[K], outv[K];
-  int ti[K], outi[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { tv[i] = -INFINITY; ti[i] = -1; }
-  for (int c = lane; c < nblocks * K; c += 64) {
-    const size_t o = ((size_t)(c / K) * B + row) * K + c % K;
-    const int vi = ci[o];
-    if (vi >= 0) topk_insert<K>(tv, ti, cv[o], vi);
-  }
-  wave_topk<K>(tv, ti, outv, outi);
-  const bool hit = outv[0] > thresh && outv[0] != INFINITY;  // NaN > thresh is false
-  if (lane == 0) {
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      if (sims) sims[(size_t)row * K + t] = unkey(outv[t]);
-      if (idx) idx[(size_t)row * K + t] = outi[t];
-    }
-    if (disc) disc[(size_t)row * disc_stride] = hit ? outv[0] : 0.f;
-  }
-  if (tsim) {
-    float d = 0.f;
-    if (hit && temb && title) d = wave_rowdot(temb + (size_t)row * D, title + (size_t)outi[0] * D, D, lane);
-    if (lane == 0) tsim[row] = d;
-  }
-}
-
-// top-k for 8 < k <= 64 on a vault of more than 16384 rows: the vault is walked in chunks of 16384
-// rows, each through the similarity and sort kernels above into [chunk][B][k] candidates (similarities
-// with NaN restored, chunk-local indices, -1 padding); this kernel sorts a query's chunks * k <= P
-// candidates under the same order and runs the sort kernel's epilogue.
-template <int P>
-__global__ __launch_bounds__(1024) void vault_sort_cand_kernel(const float* cs, const int32_t* cidx, int chunks,
-                                                               int chunk_rows, int B, int k, float thresh, float* sims,
-                                                               int32_t* idx, float* disc, int disc_stride,
-                                                               const float* temb, const float* title, int D,
-                                                               float* tsim) {
-  __shared__ float key[P];
-  __shared__ int id[P];
-  const int row = blockIdx.x, tid = threadIdx.x, n = chunks * k;
-  for (int i = tid; i < P; i += 1024) {
-    float kv = -INFINITY;
-    int ki = -1;
-    if (i < n) {
-      const int c = i / k;
-      const size_t o = ((size_t)c * B + row) * k + i % k;
-      const int li = cidx[o];
-      if (li >= 0) { kv = rank_key(cs[o]); ki = c * chunk_rows + li; }
-    }
-    key[i] = kv;
-    id[i] = ki;
-  }
-  __syncthreads();
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P / 2; i += 1024) {
-        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const float a = key[lo], b = key[hi];
-        const int ia = id[lo], ib = id[hi];
-        if (desc ? better(b, ib, a, ia) : better(a, ia, b, ib)) {
-          key[lo] = b; key[hi] = a;
-          id[lo] = ib; id[hi] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const bool hit = key[0] > thresh && key[0] != INFINITY;
-  for (int t = tid; t < k; t += 1024) {
-    if (sims) sims[(size_t)row * k + t] = unkey(key[t]);
-    if (idx) idx[(size_t)row * k + t] = id[t];
-  }
-  if (tid == 0 && disc) disc[(size_t)row * disc_stride] = hit ? key[0] : 0.f;
-  if (tsim && tid < 64) {
-    float d = 0.f;
-    if (hit && temb && title) {
-      for (int c = tid; c < D; c += 64) d = fmaf(temb[(size_t)row * D + c], title[(size_t)id[0] * D + c], d);
-      d = wave_sum(d);
-    }
-    if (tid == 0) tsim[row] = d;
-  }
 }
 
 }  // namespace
@@ -841,103 +277,6 @@ hipError_t launch_mixed_finish(const MixedFinishArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(mixed_finish_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
   return hipGetLastError();
-}
-
-#ifndef MMF_VAULT_CH
-#define MMF_VAULT_CH 4  // 16-deep K chunks per LDS stage / barrier
-#endif
-hipError_t launch_vault_sims(const float* q, const float* v, float* S, int B, int N, int D, hipStream_t s, int ref) {
-  if (D & 63) return hipErrorInvalidValue;
-  if (B <= 0 || N <= 0) return hipSuccess;
-  // the fp32-MFMA kernel; ref (option vault_ref, diagnostic): the VALU kernel it is bit-identical to
-  // (tests/test_gpu_vault_edge.py::test_vault_kernels_match_reference_kernels)
-  if (ref)
-    hipLaunchKernelGGL(vault_sims_kernel, dim3((N + 63) / 64, (B + 15) / 16), dim3(256), 0, s, q, v, S, B, N, D);
-  else if ((D % (16 * MMF_VAULT_CH)) == 0)
-    hipLaunchKernelGGL(vault_sims_mfma_kernel<MMF_VAULT_CH>, dim3((N + 63) / 64, (B + 15) / 16), dim3(256), 0, s, q, v, S, B, N, D);
-  else
-    hipLaunchKernelGGL(vault_sims_mfma_kernel<1>, dim3((N + 63) / 64, (B + 15) / 16), dim3(256), 0, s, q, v, S, B, N, D);
-  return hipGetLastError();
-}
-
-hipError_t launch_vault_topk(const float* S, int B, int N, int k, float thresh, float* sims, int32_t* idx,
-                             float* disc, int disc_stride, const float* text_emb, const float* title_emb, int D,
-                             float* text_sim, hipStream_t s, int ref) {
-  const dim3 grid(B), blk(256);  // one block (four waves) per query row
-#define TOPK_CASE(KK)                                                                                          \
-  case KK:                                                                                                     \
-    hipLaunchKernelGGL(vault_topk_kernel<KK>, grid, blk, 0, s, S, B, N, thresh, sims, idx, disc, disc_stride, \
-                       text_emb, title_emb, D, text_sim);                                                      \
-    break;
-  // k > N is the reference's argsort(...)[-k:] on a short vault: it keeps all N rows.  The
-  // register kernels pad slots N..k-1 with (-inf, -1) (the host drops idx < 0), so a fixed k = 5
-  // (mmf_analyze_batch) serves a vault of any size; the sort kernel pads the same way up to P.
-  if (k < 1 || N < 1) return hipErrorInvalidValue;
-  // ref (option vault_ref, diagnostic): every k through the full-sort kernel -- an independent
-  // selection algorithm the register kernels must agree with bit for bit
-  switch (ref && N <= 16384 ? 0 : k) {
-    TOPK_CASE(1) TOPK_CASE(2) TOPK_CASE(3) TOPK_CASE(4) TOPK_CASE(5) TOPK_CASE(6) TOPK_CASE(7) TOPK_CASE(8)
-    default: {
-#define SORT_CASE(PP)                                                                                            \
-  if (N <= PP && k <= PP) {                                                                                      \
-    hipLaunchKernelGGL(vault_sort_topk_kernel<PP>, dim3(B), dim3(1024), 0, s, S, B, N, k, thresh, sims, idx, disc, \
-                       disc_stride, text_emb, title_emb, D, text_sim);                                          \
-    return hipGetLastError();                                                                                    \
-  }
-      SORT_CASE(2048) SORT_CASE(4096) SORT_CASE(8192) SORT_CASE(16384)
-#undef SORT_CASE
-      return hipErrorInvalidValue;
-    }
-  }
-#undef TOPK_CASE
-  return hipGetLastError();
-}
-
-int vault_search_blocks(int B, int N, int nblocks) {
-  if (nblocks > 0) return nblocks;
-  const int tiles = (N + 63) / 64, gy = (B + kVsQ - 1) / kVsQ;
-  return std::max(1, std::min(tiles, kVsAuto / gy));
-}
-
-size_t vault_search_ws_bytes(int B, int k, int nblocks) {
-  return (size_t)(nblocks > 0 ? nblocks : kVsAuto) * B * k * (sizeof(float) + sizeof(int32_t));
-}
-
-hipError_t launch_vault_search(const float* q, const float* v, int B, int N, int k, float thresh, float* sims,
-                               int32_t* idx, float* disc, int disc_stride, const float* text_emb,
-                               const float* title_emb, float* text_sim, void* ws, int nblocks, hipStream_t s) {
-  if (B < 1 || N < 1 || k < 1 || k > 8 || nblocks < 0 || !ws) return hipErrorInvalidValue;
-  const int nb = vault_search_blocks(B, N, nblocks);
-  float* cv = (float*)ws;
-  int* ci = (int*)(cv + (size_t)nb * B * k);
-  const dim3 grid(nb, (B + kVsQ - 1) / kVsQ);
-#define SEARCH_CASE(KK)                                                                                          \
-  case KK:                                                                                                       \
-    hipLaunchKernelGGL(vault_search_partial_kernel<KK>, grid, dim3(256), 0, s, q, v, B, N, cv, ci);             \
-    hipLaunchKernelGGL(vault_search_merge_kernel<KK>, dim3(B), dim3(64), 0, s, cv, ci, nb, B, thresh, sims, idx, \
-                       disc, disc_stride, text_emb, title_emb, 512, text_sim);                                   \
-    break;
-  switch (k) {
-    SEARCH_CASE(1) SEARCH_CASE(2) SEARCH_CASE(3) SEARCH_CASE(4) SEARCH_CASE(5) SEARCH_CASE(6) SEARCH_CASE(7) SEARCH_CASE(8)
-  }
-#undef SEARCH_CASE
-  return hipGetLastError();
-}
-
-hipError_t launch_vault_sort_cand(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
-                                  float thresh, float* sims, int32_t* idx, float* disc, int disc_stride,
-                                  const float* text_emb, const float* title_emb, int D, float* text_sim,
-                                  hipStream_t s) {
-  if (chunks < 1 || k < 1 || B < 1) return hipErrorInvalidValue;
-#define CAND_CASE(PP)                                                                                              \
-  if ((long long)chunks * k <= PP) {                                                                               \
-    hipLaunchKernelGGL(vault_sort_cand_kernel<PP>, dim3(B), dim3(1024), 0, s, cs, cidx, chunks, chunk_rows, B, k,  \
-                       thresh, sims, idx, disc, disc_stride, text_emb, title_emb, D, text_sim);                    \
-    return hipGetLastError();                                                                                      \
-  }
-  CAND_CASE(2048) CAND_CASE(16384)
-#undef CAND_CASE
-  return hipErrorInvalidValue;
 }
 
 namespace {

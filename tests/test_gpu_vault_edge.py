@@ -123,6 +123,35 @@ def test_vault_kernels_match_reference_kernels(engine, N):
         engine.set_option("vault_ref", old)
 
 
+def test_sort_kernel_caption_similarity_matches_register_kernel(engine):
+    """The sort kernel's top-1 epilogue with a caption at a run-time k > 8 (no other test gives it
+    titles): the discrepancy, the caption-title similarity and the first five (similarity, index)
+    pairs are bit-equal at k = 5, 8 (register kernel) and k = 9, 64 (LDS sort).  The set-up is
+    test_vault_kernels_match_reference_kernels': N = 1001 with titles, 8 queries, five planted hits."""
+    N, B = 1001, 8
+    rng = np.random.default_rng(N)
+    vault = rng.standard_normal((N, 512)).astype(np.float32)
+    q = rng.standard_normal((B, 512)).astype(np.float32)
+    q[:5] = vault[rng.integers(0, N, 5)] * 3.0  # planted hits above the 0.85 threshold
+    ids = np.full((N, 77), 49407, np.int32)
+    ids[:, 0] = 49406
+    mask = np.zeros_like(ids)
+    mask[:, :2] = 1
+    engine.set_vault(vault, ids, mask)
+    qu = torch.as_tensor(q / np.linalg.norm(q, axis=1, keepdims=True)).cuda()
+    temb = torch.nn.functional.normalize(torch.randn(B, 512, generator=torch.Generator().manual_seed(N))).cuda()
+    outs = {k: [t.clone() for t in engine.vault_topk(qu, k, 0.85, temb)] for k in (5, 8, 9, 64)}
+    torch.cuda.synchronize()
+    def bits(t):
+        return t.contiguous().view(torch.int32)
+
+    sims5, idx5, disc5, tsim5 = outs[5]
+    for k, (sims, idx, disc, tsim) in outs.items():
+        assert torch.equal(bits(disc), bits(disc5)) and torch.equal(bits(tsim), bits(tsim5)), k
+        assert torch.equal(bits(sims[:, :5]), bits(sims5)) and torch.equal(idx[:, :5], idx5), k
+    assert (tsim5 != 0).any() and (tsim5 == 0).any()
+
+
 def test_vault_reload_frees_device_memory(engine):
     """mmf_set_vault_normalized / mmf_set_vault_titles replace (and free) the previous vault: ten
     reloads leave the handle's device bytes and the device's free memory where they were."""
