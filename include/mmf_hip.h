@@ -102,6 +102,52 @@ int mmf_clip_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B,
 int mmf_clip_consistency(mmf_handle* h, const uint8_t* img, const int32_t* ids, const int32_t* mask, int B, int L,
                          float* img_emb, float* txt_emb, float* sim, void* stream);
 
+/* The frozen part of CLIPDetective (train_clip_detective.py:89-99, 119-122: what every minibatch of
+ * every epoch recomputes there): the pooled rows the projection heads read.  Inputs as those of the
+ * consistency call above; img_pooled fp32 [B, 768] = post_layernorm of the CLS row, txt_pooled fp32
+ * [B, 512] = final_layer_norm of the EOS row.  Either output may be NULL: that tower is not run (its
+ * inputs may then be NULL too).  Same towers, streams and stream precision as the embedding calls. */
+int mmf_clip_pooled(mmf_handle* h, const uint8_t* img, const int32_t* ids, const int32_t* mask, int B, int L,
+                    float* img_pooled, float* txt_pooled, void* stream);
+
+/* Trained projection heads back into a handle (the load_state_dict of train_clip_detective.py:498-500
+ * for the two trained matrices): device fp32 visual [512][768] / text [512][512], rounded to fp16
+ * into the buffers the towers read.  Either may be NULL.  Allocates nothing. */
+int mmf_set_clip_projections(mmf_handle* h, const float* visual_f32, const float* text_f32, void* stream);
+
+/* CLIPDetective training on cached pooled features (train_clip_detective.py:129-166 the loss,
+ * :203-225 the loop body of train_epoch): ONE epoch.  For each of the ceil(N / batch) minibatches:
+ * e = P W^T per tower, divided by its row norm (no epsilon); logits = exp(logit_scale) I T^T; the mean
+ * of the two cross-entropies against the diagonal; backward to all three parameters; clip_grad_norm_
+ * over them together (coefficient max_norm / (norm + 1e-6), clamped at 1, always applied);
+ * torch.optim.AdamW (decoupled decay on all three, bias correction by step0 + s + 1).  No handle;
+ * asynchronous on `stream` as a chain of ordinary launches (no grid barrier, no atomics).  All fp32;
+ * every reduction has a fixed order, so results are bit-reproducible and do not depend on how an
+ * epoch is split into launches.
+ *   img_feat fp32 [N][768], txt_feat fp32 [N][512]; perm int32 [N]: minibatch s takes positions
+ *     s*batch .. of perm (the last may be short); an entry outside [0, N) is clamped.
+ *   params, exp_avg, exp_avg_sq fp32 [MMF_CLIP_TRAIN_PARAMS], updated in place.
+ *   step_loss fp32 [nsteps]: the minibatch loss before its update; step_gnorm fp32 [nsteps]: the
+ *     unclipped total norm; grad_out fp32 [MMF_CLIP_TRAIN_PARAMS] or NULL: the last minibatch's
+ *     clipped gradient.
+ *   ws: ws_bytes >= what the sizing call returns for `batch` (0 for a batch outside 1..64).
+ * Pointers are 16-byte aligned.  A 1-row minibatch has loss 0 and gradient 0; AdamW still decays the
+ * parameters.  MMF_EINVAL with nothing launched: a NULL required pointer, N < 1, batch outside 1..64,
+ * a short ws. */
+#define MMF_CLIP_TRAIN_PARAMS 655361  /* visual_projection.weight[512][768], text_projection.weight[512][512], logit_scale */
+int64_t mmf_clip_train_ws_bytes(int batch);
+int mmf_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, const int32_t* perm, int batch,
+                         double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                         int step0, float* params, float* exp_avg, float* exp_avg_sq, float* step_loss,
+                         float* step_gnorm, float* grad_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* validate (train_clip_detective.py:236-273) on cached features: forward only, consecutive batches
+ * in file order.  batch_loss fp32 [ceil(N / batch)]: the contrastive loss of each batch; row_cos
+ * fp32 [N]: each pair's own cosine (calculate_accuracy's operand, :169-187).  ws and the errors as
+ * the training call's. */
+int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch, const float* params,
+                              float* batch_loss, float* row_cos, void* ws, int64_t ws_bytes, void* stream);
+
 /* Host-input geometry on the device (misinfo_forensics.py:249-253 and the
  * CLIPImageProcessor the reference calls at :386-401): B decoded uint8 images (HWC, pixel_bytes =
  * 3 for RGB or 4 for RGBX -- Pillow's in-memory layout --, any size up to a 47x downscale)

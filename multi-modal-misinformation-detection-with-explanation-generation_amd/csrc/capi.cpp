@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 
 #include "handle.h"
 
@@ -618,6 +619,95 @@ int mmf_clip_consistency(mmf_handle* h, const uint8_t* img, const int32_t* ids, 
     HIPCHK(hipStreamWaitEvent(s, h->join_ev[2], 0));
   }
   HIPCHK(launch_rowdot(ie, te, sim, 1, B, 512, s));
+  return 0;
+}
+
+int mmf_clip_pooled(mmf_handle* h, const uint8_t* img, const int32_t* ids, const int32_t* mask, int B, int L,
+                    float* img_pooled, float* txt_pooled, void* stream) {
+  if (!h || (img_pooled && !img) || (txt_pooled && (!ids || !mask))) return fail(MMF_EINVAL, "null argument");
+  const int need = (img_pooled ? RDY_VISION : 0) | (txt_pooled ? RDY_CTEXT : 0);
+  if ((h->ready & need) != need) return fail(MMF_EINVAL, "CLIP towers not loaded");
+  if (!txt_pooled) L = 1;
+  if (L < 1 || L > 77) return fail(MMF_EINVAL, "CLIP text length %d outside 1..77", L);
+  CHK(check_cap(h, B, 1, L));
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!img_pooled || !txt_pooled) {
+    if (img_pooled) return run_clip_image_pooled(h, img, B, img_pooled, s);
+    if (txt_pooled) return run_clip_text_pooled(h, ids, mask, B, L, txt_pooled, s);
+    return 0;
+  }
+  CHK(ensure_towers(h));
+  const int concurrent = h->opt.concurrent && !h->prof;
+  hipStream_t st = s;
+  if (concurrent) {  // the text tower beside the vision tower, as the consistency call
+    HIPCHK(hipEventRecord(h->fork_ev, s));
+    HIPCHK(hipStreamWaitEvent(h->tower[2], h->fork_ev, 0));
+    st = h->tower[2];
+  }
+  CHK(run_clip_text_pooled(h, ids, mask, B, L, txt_pooled, st));
+  CHK(run_clip_image_pooled(h, img, B, img_pooled, s));
+  if (concurrent) {
+    HIPCHK(hipEventRecord(h->join_ev[2], h->tower[2]));
+    HIPCHK(hipStreamWaitEvent(s, h->join_ev[2], 0));
+  }
+  return 0;
+}
+
+int mmf_set_clip_projections(mmf_handle* h, const float* visual_f32, const float* text_f32, void* stream) {
+  if (!h) return fail(MMF_EINVAL, "null argument");
+  const int need = (visual_f32 ? RDY_VISION : 0) | (text_f32 ? RDY_CTEXT : 0);
+  if ((h->ready & need) != need || (visual_f32 && !h->v_proj) || (text_f32 && !h->t_proj))
+    return fail(MMF_EINVAL, "CLIP towers not loaded");
+  if (((uintptr_t)visual_f32 | (uintptr_t)text_f32) & 15) return fail(MMF_EINVAL, "projections must be 16-byte aligned");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (visual_f32) HIPCHK(launch_f32_to_f16(visual_f32, h->v_proj, (size_t)512 * 768, s));
+  if (text_f32) HIPCHK(launch_f32_to_f16(text_f32, h->t_proj, (size_t)512 * 512, s));
+  return 0;
+}
+
+int64_t mmf_clip_train_ws_bytes(int batch) { return (int64_t)clip_train_ws_bytes(batch); }
+
+namespace {
+bool misaligned16(std::initializer_list<const void*> ps) {
+  uintptr_t a = 0;
+  for (const void* p : ps) a |= (uintptr_t)p;
+  return (a & 15) != 0;
+}
+}  // namespace
+
+int mmf_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, const int32_t* perm, int batch,
+                         double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                         int step0, float* params, float* exp_avg, float* exp_avg_sq, float* step_loss,
+                         float* step_gnorm, float* grad_out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!img_feat || !txt_feat || !perm || !params || !exp_avg || !exp_avg_sq || !step_loss || !step_gnorm || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  if (N < 1 || batch < 1 || batch > 64 || step0 < 0)
+    return fail(MMF_EINVAL, "clip_train_epoch: N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0)", N, batch, step0);
+  if (ws_bytes < (int64_t)clip_train_ws_bytes(batch))
+    return fail(MMF_EINVAL, "clip_train_epoch: ws of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)clip_train_ws_bytes(batch));
+  if (misaligned16({img_feat, txt_feat, params, exp_avg, exp_avg_sq, grad_out, ws}))
+    return fail(MMF_EINVAL, "clip_train_epoch: pointers must be 16-byte aligned");
+  HIPCHK(launch_clip_train_epoch(img_feat, txt_feat, N, perm, batch, lr, beta1, beta2, eps, weight_decay, max_norm,
+                                 step0, params, exp_avg, exp_avg_sq, step_loss, step_gnorm, grad_out, (float*)ws,
+                                 (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch, const float* params,
+                              float* batch_loss, float* row_cos, void* ws, int64_t ws_bytes, void* stream) {
+  if (!img_feat || !txt_feat || !params || !batch_loss || !row_cos || !ws) return fail(MMF_EINVAL, "null argument");
+  if (N < 1 || batch < 1 || batch > 64)
+    return fail(MMF_EINVAL, "clip_contrastive_eval: N=%d (>= 1) batch=%d (1..64)", N, batch);
+  if (ws_bytes < (int64_t)clip_train_ws_bytes(batch))
+    return fail(MMF_EINVAL, "clip_contrastive_eval: ws of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)clip_train_ws_bytes(batch));
+  if (misaligned16({img_feat, txt_feat, params, ws}))
+    return fail(MMF_EINVAL, "clip_contrastive_eval: pointers must be 16-byte aligned");
+  HIPCHK(launch_clip_contrastive_eval(img_feat, txt_feat, N, batch, params, batch_loss, row_cos, (float*)ws,
+                                      (hipStream_t)stream));
   return 0;
 }
 

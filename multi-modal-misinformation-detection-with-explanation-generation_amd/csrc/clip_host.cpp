@@ -256,3 +256,22 @@ int run_clip_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B,
   const Workspace& w = h->ws;
   return clip_tail(h, w.t_xc, h->t_final, w.t_pool, h->t_proj, 512, w.sk_ctext, B, emb, s);
 }
+
+// The towers up to clip_tail's LayerNorm, its fp32 leg alone: what the projection heads read
+// (train_clip_detective.py:119-122 with the encoders frozen, :89-99)
+int run_clip_image_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, hipStream_t s) {
+  CHK(clip_image_embed(h, img, B, s));
+  ClipEnc E = vit_enc(h, B);
+  CHK(run_clip_encoder(h, E, 0, 12, s));
+  HIPCHK(launch_gather_ln(h->ws.v_xc, nullptr, 1, h->v_post.g, h->v_post.b, 1e-5f, nullptr, pooled, B, 768, s));
+  return 0;
+}
+
+int run_clip_text_pooled(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* pooled,
+                         hipStream_t s) {
+  CHK(clip_text_embed(h, ids, B, L, s));
+  ClipEnc E = text_enc(h, mask, B, L);
+  CHK(run_clip_encoder(h, E, 0, 12, s));
+  HIPCHK(launch_gather_ln(h->ws.t_xc, nullptr, 1, h->t_final.g, h->t_final.b, 1e-5f, nullptr, pooled, B, 512, s));
+  return 0;
+}

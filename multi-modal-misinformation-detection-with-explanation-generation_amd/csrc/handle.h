@@ -475,6 +475,10 @@ int run_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int 
              float* scores, int score_stride, hipStream_t s, hipEvent_t heads_ev = nullptr);
 int run_clip_image(mmf_handle* h, const uint8_t* img, int B, float* emb, hipStream_t s);
 int run_clip_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* emb, hipStream_t s);
+// the same towers up to the pooled LayerNorm: fp32 post_layernorm(CLS) [B][768] / final_layer_norm(EOS) [B][512]
+int run_clip_image_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, hipStream_t s);
+int run_clip_text_pooled(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* pooled,
+                         hipStream_t s);
 // a chunk starting at image img0 works in its own slice of every workspace (mmf_effnet_forward)
 int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score, int score_stride,
                hipStream_t s, int img0 = 0);

@@ -153,6 +153,21 @@ hipError_t launch_fusion_train_epoch(const float* scores5, const int32_t* labels
                                      double beta2, double eps, double weight_decay, int step0, float* params,
                                      float* exp_avg, float* exp_avg_sq, float* step_loss, int32_t* step_correct,
                                      float* grad_out, hipStream_t s);
+// CLIPDetective's projection heads on cached pooled features (clip_train.hip; include/mmf_hip.h
+// mmf_clip_train_epoch / mmf_clip_contrastive_eval): six launches per minibatch (three for the eval), ws of
+// clip_train_ws_bytes(batch) bytes (0 for a batch outside 1..64); hipErrorInvalidValue on a bad N / batch with
+// nothing launched
+constexpr int kClipTrainParams = 655361;  // visual [512][768] | text [512][512] | logit_scale
+size_t clip_train_ws_bytes(int batch);
+hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, const int32_t* perm, int batch,
+                                   double lr, double beta1, double beta2, double eps, double weight_decay,
+                                   double max_norm, int step0, float* params, float* exp_avg, float* exp_avg_sq,
+                                   float* step_loss, float* step_gnorm, float* grad_out, float* ws, hipStream_t s);
+hipError_t launch_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch,
+                                        const float* params, float* batch_loss, float* row_cos, float* ws,
+                                        hipStream_t s);
+// dst fp16 [n] = round-to-nearest-even of src fp32 [n] (n a multiple of 4, 16-byte aligned)
+hipError_t launch_f32_to_f16(const float* src, f16_t* dst, size_t n, hipStream_t s);
 // mmf_analyze_mixed's last kernel: per batch row, the row's compact tower results gathered through
 // row_map [B][3] (position of the row in the text / image / both lists; anything outside [0, n) is
 // absent), the CLIP cosine and the caption-title cosine of the "both" rows, the vault outputs scattered

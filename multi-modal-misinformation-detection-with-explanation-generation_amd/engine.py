@@ -485,6 +485,97 @@ class Engine:
               "mmf_clip_consistency")
         return out
 
+    def clip_pooled(self, img, ids, mask):
+        """The rows CLIPDetective's projection heads read (mmf_clip_pooled): (post_layernorm(CLS) float32
+        [B, 768], final_layer_norm(EOS) float32 [B, 512]) on the device; ``img`` None or ``ids`` None skips
+        that tower (its result is None).  The fp16-stream overflow trap of the synchronous API paths: a
+        non-finite row switches the towers to fp32 streams and the batch runs again."""
+        img = self._u8(img) if img is not None else None
+        ids, mask = (self._i32(ids), self._i32(mask)) if ids is not None else (None, None)
+        if img is None and ids is None:
+            raise ValueError("clip_pooled: no input")
+        B = img.shape[0] if img is not None else ids.shape[0]
+        ip = self._f32(B, 768) if img is not None else None
+        tp = self._f32(B, 512) if ids is not None else None
+
+        def run():
+            check(self.lib.mmf_clip_pooled(self.h, ptr(img), ptr(ids), ptr(mask), B, ids.shape[1] if ids is not None
+                                           else 1, ptr(ip), ptr(tp), stream_ptr()), "mmf_clip_pooled")
+        run()
+        if self.clip_stream_overflow(ip, tp):
+            run()
+        return ip, tp
+
+    def set_clip_projections(self, visual=None, text=None) -> None:
+        """Trained projection heads into the towers (mmf_set_clip_projections): float32 [512, 768] /
+        [512, 512], rounded to fp16 on the device into the buffers clip_image / clip_text read; nothing is
+        allocated."""
+        def prep(w, cols):
+            if w is None:
+                return None
+            t = torch.as_tensor(w, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(t.shape) != (512, cols):
+                raise ValueError(f"projection must be [512, {cols}], got {tuple(t.shape)}")
+            return t
+        v, t = prep(visual, 768), prep(text, 512)
+        check(self.lib.mmf_set_clip_projections(self.h, ptr(v), ptr(t), stream_ptr()), "mmf_set_clip_projections")
+        torch.cuda.current_stream().synchronize()  # v / t may be temporaries
+
+    CLIP_TRAIN_PARAMS = 655361  # MMF_CLIP_TRAIN_PARAMS: visual [512][768] | text [512][512] | logit_scale
+
+    def _clip_train_ws(self, batch: int) -> torch.Tensor:
+        need = int(self.lib.mmf_clip_train_ws_bytes(int(batch)))
+        ws = getattr(self, "_ct_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._ct_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _clip_train_check(self, what: str, tensors) -> None:
+        for name, t, dt, n, optional in tensors:
+            if t is None and optional:
+                continue
+            if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.is_contiguous()
+                    and t.numel() == n):
+                raise ValueError(f"{what}: {name} must be a contiguous {dt} tensor of {n} elements on {self.device}")
+
+    def clip_train_epoch(self, img_feat, txt_feat, perm, batch: int, lr: float, betas, eps: float,
+                         weight_decay: float, max_norm: float, step0: int, params, exp_avg, exp_avg_sq,
+                         grad_out=None):
+        """One epoch of projection-head training on cached pooled features (mmf_clip_train_epoch): device
+        tensors img_feat float32 [N, 768], txt_feat float32 [N, 512], perm int32 [N]; params / exp_avg /
+        exp_avg_sq float32 [655361], updated in place.  Returns (step_loss, step_gnorm) float32 [nsteps] on
+        the device; nothing is synchronised."""
+        N, P = int(perm.shape[0]), self.CLIP_TRAIN_PARAMS
+        self._clip_train_check("clip_train_epoch", (
+            ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
+            ("perm", perm, torch.int32, N, False), ("params", params, torch.float32, P, False),
+            ("exp_avg", exp_avg, torch.float32, P, False), ("exp_avg_sq", exp_avg_sq, torch.float32, P, False),
+            ("grad_out", grad_out, torch.float32, P, True)))
+        nsteps = max(1, -(-N // max(1, int(batch))))
+        step_loss, step_gnorm = self._f32(nsteps), self._f32(nsteps)
+        ws = self._clip_train_ws(batch)
+        check(self.lib.mmf_clip_train_epoch(ptr(img_feat), ptr(txt_feat), N, ptr(perm), int(batch), float(lr),
+                                            float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                            float(max_norm), int(step0), ptr(params), ptr(exp_avg), ptr(exp_avg_sq),
+                                            ptr(step_loss), ptr(step_gnorm), ptr(grad_out), ptr(ws), ws.numel(),
+                                            stream_ptr()), "mmf_clip_train_epoch")
+        return step_loss, step_gnorm
+
+    def clip_contrastive_eval(self, img_feat, txt_feat, batch: int, params):
+        """validate's forward on cached features (mmf_clip_contrastive_eval): consecutive batches in row
+        order -> (batch_loss float32 [nbatches], row_cos float32 [N]) on the device."""
+        N = int(img_feat.shape[0])
+        self._clip_train_check("clip_contrastive_eval", (
+            ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
+            ("params", params, torch.float32, self.CLIP_TRAIN_PARAMS, False)))
+        nb = max(1, -(-N // max(1, int(batch))))
+        batch_loss, row_cos = self._f32(nb), self._f32(N)
+        ws = self._clip_train_ws(batch)
+        check(self.lib.mmf_clip_contrastive_eval(ptr(img_feat), ptr(txt_feat), N, int(batch), ptr(params),
+                                                 ptr(batch_loss), ptr(row_cos), ptr(ws), ws.numel(), stream_ptr()),
+              "mmf_clip_contrastive_eval")
+        return batch_loss, row_cos
+
     def vault_topk(self, q_unit: torch.Tensor, k: int = 5, thresh: float = 0.85, text_emb=None):
         q = q_unit.contiguous()
         B = q.shape[0]

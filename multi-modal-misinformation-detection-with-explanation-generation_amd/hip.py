@@ -31,6 +31,12 @@ SIGNATURES = {
     "mmf_clip_image": (_I, [_P, _P, _I, _P, _P]),
     "mmf_clip_text": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "mmf_clip_consistency": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mmf_clip_pooled": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "mmf_set_clip_projections": (_I, [_P, _P, _P, _P]),
+    "mmf_clip_train_ws_bytes": (ctypes.c_int64, [_I]),
+    "mmf_clip_train_epoch": (_I, [_P, _P, _I, _P, _I, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P,
+                                  ctypes.c_int64, _P]),
+    "mmf_clip_contrastive_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "mmf_resize_pil": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mmf_resize_supported": (_I, [_I, _I]),
     "mmf_jpeg_header": (_I, [_P, ctypes.c_int64, _P]),
