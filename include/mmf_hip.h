@@ -75,6 +75,55 @@ int mmf_reserve(mmf_handle* h, int max_batch, int max_text_len, int max_clip_len
 int mmf_text_forward(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L,
                      float* ai_logits, float* misinfo_logits, float* scores2, void* stream);
 
+/* The frozen part of the text-head training script (train_ai_head.py:415-420 freezes everything but the
+ * head, :224-230 runs the whole encoder for every minibatch of every epoch): the rows the two heads read,
+ * outputs.last_hidden_state[:, 0, :] (misinfo_forensics.py:95).  ids/mask as mmf_text_forward; cls fp32
+ * [B, 768], 16-byte aligned.  The launch sequence of mmf_text_forward in the stream layout in use
+ * (fp16, split or precise), without the heads; a sequence whose fp16 stream overflowed gets a NaN row, as
+ * it gets NaN logits there. */
+int mmf_text_pooled(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* cls, void* stream);
+
+/* Training of one RoBERTa text head -- ai_head or misinfo_head, Linear(768,256)-ReLU-Dropout-Linear(256,2)
+ * (misinfo_forensics.py:57-69) -- on cached CLS rows (train_ai_head.py:206-255 the loop body of train_epoch,
+ * stated for the deployed head): ONE epoch.  For each of the ceil(N / batch) minibatches: pre = X W1^T +
+ * b1; h = relu(pre) * keep * scale, scale = fp32 of 1 / (1 - p_drop) computed in double; logits = h W2^T +
+ * b2; mean cross-entropy; backward to all four tensors; clip_grad_norm_ over them together (coefficient
+ * max_norm / (norm + 1e-6), clamped at 1, always applied); torch.optim.AdamW (decoupled decay on all four,
+ * bias correction by step0 + s + 1) with the learning rate lr_steps[s] of that step (the script steps its
+ * warmup-cosine schedule after every minibatch, :241; a step with lr 0 leaves the parameters bit-unchanged
+ * and still updates the moments).  No handle; asynchronous on `stream` as a chain of four ordinary
+ * launches per minibatch (no grid barrier, no atomics).  All fp32; every reduction has a fixed order
+ * (csrc/head_train.hip), so results are bit-reproducible and do not depend on how an epoch is split into
+ * launches.
+ *   feat fp32 [N][768]; labels int32 [N], read as label & 1; perm int32 [N]: minibatch s takes positions
+ *     s*batch .. of perm (the last may be short; its mean is over its own rows); an entry outside [0, N)
+ *     is clamped, so no input makes a kernel read out of bounds.
+ *   keep uint64 [N][4] or NULL: keep[i] is the dropout mask of the row at POSITION i of the epoch order,
+ *     word w bit j set = hidden unit 64 w + j kept and scaled; NULL = no dropout, no scaling.
+ *   lr_steps: HOST double [nsteps], read before the call returns.
+ *   params, exp_avg, exp_avg_sq fp32 [MMF_HEAD_PARAMS], state-dict order, updated in place.
+ *   step_loss fp32 [nsteps]: the minibatch's mean loss (train-mode logits, before its update); step_correct
+ *     int32 [nsteps]: rows with argmax(logits) == label (a tie is class 0, as torch.argmax); step_gnorm fp32
+ *     [nsteps]: the unclipped total norm; grad_out fp32 [MMF_HEAD_PARAMS] or NULL: the last minibatch's
+ *     clipped gradient.
+ *   ws: ws_bytes >= what the sizing call returns for `batch` (0 for a batch outside 1..64).
+ * feat, params, the moments, grad_out and ws are 16-byte aligned, keep 8-byte.  MMF_EINVAL with nothing
+ * launched: a NULL required pointer, N < 1, batch outside 1..64, p_drop outside [0, 1), a short or
+ * misaligned ws. */
+#define MMF_HEAD_PARAMS 197378  /* 0.weight[256][768], 0.bias[256], 3.weight[2][256], 3.bias[2] */
+int64_t mmf_head_train_ws_bytes(int batch);
+int mmf_head_train_epoch(const float* feat, const int32_t* labels, int N, const int32_t* perm, const uint64_t* keep,
+                         float p_drop, int batch, const double* lr_steps, double beta1, double beta2, double eps,
+                         double weight_decay, double max_norm, int step0, float* params, float* exp_avg,
+                         float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* step_gnorm, float* grad_out,
+                         void* ws, int64_t ws_bytes, void* stream);
+
+/* validate (train_ai_head.py:258-296) on cached CLS rows: forward only, no dropout, consecutive batches in
+ * file order.  batch_loss fp32 [ceil(N / batch)]: each batch's mean cross-entropy; row_logits fp32 [N][2].
+ * ws and the errors as the training call's. */
+int mmf_head_eval(const float* feat, const int32_t* labels, int N, int batch, const float* params, float* batch_loss,
+                  float* row_logits, void* ws, int64_t ws_bytes, void* stream);
+
 /* Signal 3 — analyze_image (misinfo_forensics.py:354-373, 249-253): ImageNet normalisation +
  * EfficientNet-B0.  img uint8 [B, 224, 224, 3] device.  logits fp32 [B, 2] (may be NULL),
  * deepfake_score fp32 [B] (may be NULL). */

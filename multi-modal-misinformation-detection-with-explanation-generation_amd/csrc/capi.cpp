@@ -530,6 +530,16 @@ int mmf_text_forward(mmf_handle* h, const int32_t* ids, const int32_t* mask, int
   return run_text(h, ids, mask, B, L, ai, mi, scores2, 2, (hipStream_t)stream);
 }
 
+int mmf_text_pooled(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* cls, void* stream) {
+  if (!h || !ids || !mask || !cls) return fail(MMF_EINVAL, "null argument");
+  if (!(h->ready & RDY_TEXT)) return fail(MMF_EINVAL, "text model (RoBERTa + heads) not loaded");
+  if (L < 1 || L > 512) return fail(MMF_EINVAL, "RoBERTa length %d outside 1..512 (position table ends at 514)", L);
+  if ((uintptr_t)cls & 15) return fail(MMF_EINVAL, "text_pooled: cls must be 16-byte aligned");
+  CHK(check_cap(h, B, L, 1));
+  HIPCHK(hipSetDevice(h->device));
+  return run_text(h, ids, mask, B, L, nullptr, nullptr, nullptr, 2, (hipStream_t)stream, nullptr, cls);
+}
+
 int mmf_effnet_forward(mmf_handle* h, const uint8_t* img, int B, float* logits, float* score, void* stream) {
   if (!h || !img) return fail(MMF_EINVAL, "null argument");
   if (!(h->ready & RDY_EFFNET)) return fail(MMF_EINVAL, "EfficientNet not loaded");
@@ -708,6 +718,42 @@ int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int 
     return fail(MMF_EINVAL, "clip_contrastive_eval: pointers must be 16-byte aligned");
   HIPCHK(launch_clip_contrastive_eval(img_feat, txt_feat, N, batch, params, batch_loss, row_cos, (float*)ws,
                                       (hipStream_t)stream));
+  return 0;
+}
+
+int64_t mmf_head_train_ws_bytes(int batch) { return (int64_t)head_train_ws_bytes(batch); }
+
+int mmf_head_train_epoch(const float* feat, const int32_t* labels, int N, const int32_t* perm, const uint64_t* keep,
+                         float p_drop, int batch, const double* lr_steps, double beta1, double beta2, double eps,
+                         double weight_decay, double max_norm, int step0, float* params, float* exp_avg,
+                         float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* step_gnorm, float* grad_out,
+                         void* ws, int64_t ws_bytes, void* stream) {
+  if (!feat || !labels || !perm || !lr_steps || !params || !exp_avg || !exp_avg_sq || !step_loss || !step_correct ||
+      !step_gnorm || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  if (N < 1 || batch < 1 || batch > 64 || step0 < 0 || !(p_drop >= 0.f && p_drop < 1.f))
+    return fail(MMF_EINVAL, "head_train_epoch: N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0) p_drop=%g ([0, 1))", N,
+                batch, step0, (double)p_drop);
+  if (ws_bytes < (int64_t)head_train_ws_bytes(batch))
+    return fail(MMF_EINVAL, "head_train_epoch: ws of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)head_train_ws_bytes(batch));
+  if (misaligned16({feat, params, exp_avg, exp_avg_sq, grad_out, ws}) || ((uintptr_t)keep & 7))
+    return fail(MMF_EINVAL, "head_train_epoch: pointers must be 16-byte aligned (keep: 8)");
+  HIPCHK(launch_head_train_epoch(feat, labels, N, perm, keep, p_drop, batch, lr_steps, beta1, beta2, eps, weight_decay,
+                                 max_norm, step0, params, exp_avg, exp_avg_sq, step_loss, step_correct, step_gnorm,
+                                 grad_out, (float*)ws, (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_head_eval(const float* feat, const int32_t* labels, int N, int batch, const float* params, float* batch_loss,
+                  float* row_logits, void* ws, int64_t ws_bytes, void* stream) {
+  if (!feat || !labels || !params || !batch_loss || !row_logits || !ws) return fail(MMF_EINVAL, "null argument");
+  if (N < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "head_eval: N=%d (>= 1) batch=%d (1..64)", N, batch);
+  if (ws_bytes < (int64_t)head_train_ws_bytes(batch))
+    return fail(MMF_EINVAL, "head_eval: ws of %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)head_train_ws_bytes(batch));
+  if (misaligned16({feat, params, ws})) return fail(MMF_EINVAL, "head_eval: pointers must be 16-byte aligned");
+  HIPCHK(launch_head_eval(feat, labels, N, batch, params, batch_loss, row_logits, (float*)ws, (hipStream_t)stream));
   return 0;
 }
 

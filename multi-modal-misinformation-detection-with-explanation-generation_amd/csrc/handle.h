@@ -472,7 +472,7 @@ inline int text_mode(const mmf_handle* h) { return h->opt.text_hilo < 0 ? h->r_h
 // heads_ev: recorded once the encoder is done, before the heads (mmf_analyze_batch's after_text event:
 // the waiting towers start while the two small head MLPs run)
 int run_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* ai, float* mi,
-             float* scores, int score_stride, hipStream_t s, hipEvent_t heads_ev = nullptr);
+             float* scores, int score_stride, hipStream_t s, hipEvent_t heads_ev = nullptr, float* cls = nullptr);
 int run_clip_image(mmf_handle* h, const uint8_t* img, int B, float* emb, hipStream_t s);
 int run_clip_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* emb, hipStream_t s);
 // the same towers up to the pooled LayerNorm: fp32 post_layernorm(CLS) [B][768] / final_layer_norm(EOS) [B][512]

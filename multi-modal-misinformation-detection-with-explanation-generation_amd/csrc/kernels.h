@@ -166,6 +166,22 @@ hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat,
 hipError_t launch_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch,
                                         const float* params, float* batch_loss, float* row_cos, float* ws,
                                         hipStream_t s);
+// a RoBERTa text head (Linear(768,256)-ReLU-Dropout-Linear(256,2)) on cached CLS rows (head_train.hip;
+// include/mmf_hip.h mmf_head_train_epoch / mmf_head_eval): four launches per minibatch (two for the eval), ws of
+// head_train_ws_bytes(batch) bytes (0 for a batch outside 1..64); lr_steps is a HOST array read at enqueue time;
+// hipErrorInvalidValue on a bad N / batch / p_drop with nothing launched
+constexpr int kHeadTrainParams = 197378;  // 0.weight [256][768] | 0.bias [256] | 3.weight [2][256] | 3.bias [2]
+size_t head_train_ws_bytes(int batch);
+hipError_t launch_head_train_epoch(const float* feat, const int32_t* labels, int N, const int32_t* perm,
+                                   const uint64_t* keep, float p_drop, int batch, const double* lr_steps, double beta1,
+                                   double beta2, double eps, double weight_decay, double max_norm, int step0,
+                                   float* params, float* exp_avg, float* exp_avg_sq, float* step_loss,
+                                   int32_t* step_correct, float* step_gnorm, float* grad_out, float* ws, hipStream_t s);
+hipError_t launch_head_eval(const float* feat, const int32_t* labels, int N, int batch, const float* params,
+                            float* batch_loss, float* row_logits, float* ws, hipStream_t s);
+// the CLS rows the text heads read: out fp32 [B][768] = x[b * row_stride ..]; a sequence with ovf[b] != 0 (nullable)
+// gets a NaN row, as launch_text_heads gives it NaN logits
+hipError_t launch_text_cls_rows(const float* x, int row_stride, const int* ovf, float* out, int B, hipStream_t s);
 // dst fp16 [n] = round-to-nearest-even of src fp32 [n] (n a multiple of 4, 16-byte aligned)
 hipError_t launch_f32_to_f16(const float* src, f16_t* dst, size_t n, hipStream_t s);
 // mmf_analyze_mixed's last kernel: per batch row, the row's compact tower results gathered through

@@ -1,6 +1,6 @@
-// Small fp32 kernels at the ends of the path: the RoBERTa dual heads, the FusionJudge MLP with
-// verdict / explanation rule, cosine rows, mmf_analyze_mixed's finish and a strided fill (the
-// Truth-Vault search is vault.hip).
+// Small fp32 kernels at the ends of the path: the RoBERTa dual heads (and a copy of the CLS rows they
+// read), the FusionJudge MLP with verdict / explanation rule, cosine rows, mmf_analyze_mixed's finish
+// and a strided fill (the Truth-Vault search is vault.hip).
 // These are latency/L2-bound: they run in exact fp32 like the reference.
 #include "common.h"
 #include "kernels.h"
@@ -83,6 +83,14 @@ __global__ __launch_bounds__(1024) void text_heads_kernel(const float* x, int ro
       scores[(size_t)row * score_stride + head] = e1 / (e0 + e1);
     }
   }
+}
+
+// The rows text_heads_kernel reads, as they are (mmf_text_pooled): 192 threads per row, a float4 each.
+__global__ __launch_bounds__(192) void text_cls_rows_kernel(const float* x, int row_stride, const int* ovf, float* out) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  float4 v = *reinterpret_cast<const float4*>(x + (size_t)b * row_stride + t * 4);
+  if (ovf && ovf[b]) v.x = v.y = v.z = v.w = __builtin_nanf("");  // the sequence's fp16 stream overflowed (norm.hip)
+  *reinterpret_cast<float4*>(out + (size_t)b * 768 + t * 4) = v;
 }
 
 // misinfo_forensics.py:575-615 (fusion_verdict) + 742-765 (fallback explanation rule cascade).
@@ -252,6 +260,12 @@ hipError_t launch_text_heads(const float* x, int row_stride, const float* w1a, c
                              int B, hipStream_t s, const int* ovf) {
   hipLaunchKernelGGL(text_heads_kernel, dim3((B + 3) / 4, 2), dim3(1024), 0, s, x, row_stride, w1a, b1a, w2a, b2a, w1m,
                      b1m, w2m, b2m, ai_logits, mi_logits, scores, score_stride, B, ovf);
+  return hipGetLastError();
+}
+
+hipError_t launch_text_cls_rows(const float* x, int row_stride, const int* ovf, float* out, int B, hipStream_t s) {
+  if (B < 1 || row_stride % 4 || (((uintptr_t)x | (uintptr_t)out) & 15)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(text_cls_rows_kernel, dim3(B), dim3(192), 0, s, x, row_stride, ovf, out);
   return hipGetLastError();
 }
 

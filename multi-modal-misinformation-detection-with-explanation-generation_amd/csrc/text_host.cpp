@@ -8,7 +8,7 @@ namespace {
 // [W_hi | W_hi | W_lo] product on the fp16 MFMA kernels.  All 12 layers run on every row; the heads
 // read the CLS rows of the final stream.  DESIGN §4 states its cost.
 int run_text_precise(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* ai, float* mi,
-                     float* scores, int score_stride, hipStream_t s) {
+                     float* scores, int score_stride, hipStream_t s, float* cls) {
   Workspace& w = h->ws;
   const int M = B * L;
   const int pm = h->opt.text_prec_mask & 15;  // kinds on hi / lo activations: [A_hi | A_lo] x [W_hi | W_hi] (K = 2 in)
@@ -82,6 +82,10 @@ int run_text_precise(mmf_handle* h, const int32_t* ids, const int32_t* mask, int
       HIPCHK(launch_layernorm(x, 768, y, 768, Ly.ln2.g, Ly.ln2.b, 1e-5f, x, 768, nullptr, 0, M, 768, s));
     }
   }
+  if (cls) {  // mmf_text_pooled: the CLS rows instead of the heads
+    HIPCHK(launch_text_cls_rows(x, L * 768, nullptr, cls, B, s));
+    return 0;
+  }
   ProfScope ps(h, s, PK_HEADS, 2.0 * B * 2 * (768 * 256 + 256 * 2), (double)B * 768 * 4 + 2 * 768 * 256 * 4);
   HIPCHK(launch_text_heads(x, L * 768, h->h_w1a, h->h_b1a, h->h_w2a, h->h_b2a, h->h_w1m, h->h_b1m, h->h_w2m,
                            h->h_b2m, ai, mi, scores, score_stride, B, s));
@@ -91,11 +95,11 @@ int run_text_precise(mmf_handle* h, const int32_t* ids, const int32_t* mask, int
 }  // namespace
 
 int run_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* ai, float* mi,
-             float* scores, int score_stride, hipStream_t s, hipEvent_t heads_ev) {
+             float* scores, int score_stride, hipStream_t s, hipEvent_t heads_ev, float* cls) {
   Workspace& w = h->ws;
   const int hilo = text_mode(h);
   if (hilo >= 2) {
-    CHK(run_text_precise(h, ids, mask, B, L, ai, mi, scores, score_stride, s));
+    CHK(run_text_precise(h, ids, mask, B, L, ai, mi, scores, score_stride, s, cls));
     if (heads_ev) HIPCHK(hipEventRecord(heads_ev, s));
     return 0;
   }
@@ -200,6 +204,10 @@ int run_text(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int 
     CHK(lnorm(h, last ? w.r_x : w.r_y, 768, Ly.ln2, w.r_x, 768, w.r_xb, 768, Mr, 768, s));
   }
   // w.r_x now holds the B final CLS rows, compact
+  if (cls) {  // mmf_text_pooled: the CLS rows instead of the heads
+    HIPCHK(launch_text_cls_rows(w.r_x, 768, ovf, cls, B, s));
+    return 0;
+  }
   if (heads_ev) HIPCHK(hipEventRecord(heads_ev, s));
   ProfScope ps(h, s, PK_HEADS, 2.0 * B * 2 * (768 * 256 + 256 * 2), (double)B * 768 * 4 + 2 * 768 * 256 * 4);
   HIPCHK(launch_text_heads(w.r_x, 768, h->h_w1a, h->h_b1a, h->h_w2a, h->h_b2a, h->h_w1m, h->h_b1m, h->h_w2m,

@@ -441,6 +441,23 @@ class Engine:
                                         stream_ptr()), "mmf_text_forward")
         return ai, mi, sc
 
+    def text_pooled(self, ids, mask):
+        """The rows the ai / misinfo heads read (mmf_text_pooled): last_hidden_state[:, 0, :] float32 [B, 768]
+        on the device, by text_forward's launch sequence without the heads.  The run-time trap of the
+        synchronous API paths (text_overflow): a non-finite row switches the tower to the precise mode and the
+        batch runs again."""
+        ids, mask = self._i32(ids), self._i32(mask)
+        B, L = ids.shape
+        cls = self._f32(B, 768)
+
+        def run():
+            check(self.lib.mmf_text_pooled(self.h, ptr(ids), ptr(mask), B, L, ptr(cls), stream_ptr()),
+                  "mmf_text_pooled")
+        run()
+        if self.text_overflow((cls * 0).sum(1).cpu().numpy()):  # 0 or NaN per row
+            run()
+        return cls
+
     def effnet_forward(self, img):
         img = self._u8(img)
         B = img.shape[0]
@@ -575,6 +592,58 @@ class Engine:
                                                  ptr(batch_loss), ptr(row_cos), ptr(ws), ws.numel(), stream_ptr()),
               "mmf_clip_contrastive_eval")
         return batch_loss, row_cos
+
+    HEAD_PARAMS = 197378  # MMF_HEAD_PARAMS: 0.weight [256][768] | 0.bias [256] | 3.weight [2][256] | 3.bias [2]
+
+    def _head_train_ws(self, batch: int) -> torch.Tensor:
+        need = int(self.lib.mmf_head_train_ws_bytes(int(batch)))
+        ws = getattr(self, "_ht_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._ht_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def head_train_epoch(self, feat, labels, perm, keep, p_drop: float, batch: int, lr_steps, betas, eps: float,
+                         weight_decay: float, max_norm: float, step0: int, params, exp_avg, exp_avg_sq,
+                         grad_out=None):
+        """One epoch of text-head training on cached CLS rows (mmf_head_train_epoch): device tensors feat
+        float32 [N, 768], labels int32 [N], perm int32 [N], keep int64 [N, 4] (the uint64 masks' bits) or
+        None; lr_steps: the nsteps learning rates (host); params / exp_avg / exp_avg_sq float32 [197378],
+        updated in place.  Returns (step_loss float32, step_correct int32, step_gnorm float32) [nsteps] on the
+        device; nothing is synchronised."""
+        N, P = int(perm.shape[0]), self.HEAD_PARAMS
+        self._clip_train_check("head_train_epoch", (
+            ("feat", feat, torch.float32, 768 * N, False), ("labels", labels, torch.int32, N, False),
+            ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, 4 * N, True),
+            ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
+            ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
+        nsteps = max(1, -(-N // max(1, int(batch))))
+        lrs = np.ascontiguousarray(np.asarray(lr_steps, dtype=np.float64).reshape(-1))
+        if lrs.shape[0] != nsteps:
+            raise ValueError(f"head_train_epoch: {lrs.shape[0]} learning rates for {nsteps} steps")
+        step_loss, step_gnorm = self._f32(nsteps), self._f32(nsteps)
+        step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
+        ws = self._head_train_ws(batch)
+        check(self.lib.mmf_head_train_epoch(ptr(feat), ptr(labels), N, ptr(perm), ptr(keep), float(p_drop), int(batch),
+                                            lrs.ctypes.data_as(ctypes.c_void_p), float(betas[0]), float(betas[1]),
+                                            float(eps), float(weight_decay), float(max_norm), int(step0), ptr(params),
+                                            ptr(exp_avg), ptr(exp_avg_sq), ptr(step_loss), ptr(step_correct),
+                                            ptr(step_gnorm), ptr(grad_out), ptr(ws), ws.numel(), stream_ptr()),
+              "mmf_head_train_epoch")
+        return step_loss, step_correct, step_gnorm
+
+    def head_eval(self, feat, labels, batch: int, params):
+        """validate's forward on cached CLS rows (mmf_head_eval): consecutive batches in row order ->
+        (batch_loss float32 [nbatches], row_logits float32 [N, 2]) on the device."""
+        N = int(labels.shape[0])
+        self._clip_train_check("head_eval", (
+            ("feat", feat, torch.float32, 768 * N, False), ("labels", labels, torch.int32, N, False),
+            ("params", params, torch.float32, self.HEAD_PARAMS, False)))
+        nb = max(1, -(-N // max(1, int(batch))))
+        batch_loss, row_logits = self._f32(nb), self._f32(N, 2)
+        ws = self._head_train_ws(batch)
+        check(self.lib.mmf_head_eval(ptr(feat), ptr(labels), N, int(batch), ptr(params), ptr(batch_loss),
+                                     ptr(row_logits), ptr(ws), ws.numel(), stream_ptr()), "mmf_head_eval")
+        return batch_loss, row_logits
 
     def vault_topk(self, q_unit: torch.Tensor, k: int = 5, thresh: float = 0.85, text_emb=None):
         q = q_unit.contiguous()

@@ -26,6 +26,11 @@ SIGNATURES = {
     "mmf_ready": (_I, [_P]),
     "mmf_reserve": (_I, [_P, _I, _I, _I]),
     "mmf_text_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mmf_text_pooled": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "mmf_head_train_ws_bytes": (ctypes.c_int64, [_I]),
+    "mmf_head_train_epoch": (_I, [_P, _P, _I, _P, _P, _F, _I, _P, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, ctypes.c_int64, _P]),
+    "mmf_head_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "mmf_effnet_forward": (_I, [_P, _P, _I, _P, _P, _P]),
     "mmf_effnet_forward_f32": (_I, [_P, _P, _I, _P, _P, _P]),
     "mmf_clip_image": (_I, [_P, _P, _I, _P, _P]),
