@@ -615,6 +615,16 @@ int mmf_gemm_splitk_factor(int M, int N, int K, int ldc);
 int mmf_gemm_f16_splitk(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res32,
                         const void* res16, float* c32, void* c16, int ldc, int M, int N, int K, int act, float* ws,
                         int64_t ws_elems, void* stream);
+/* The plain (epilogue 0) GEMM with every operand and stride independent: c = act((A * ascale) @ W^T + bias) + residual.
+ * A fp16 [M][K] lda, W fp16 [N][K] ldw, bias fp32 [N] (nullable), at most one of res32 fp32 / res16 fp16 [M][N] ldr
+ * (ldr >= N, ldr % 4 == 0; res32 may alias c32), ascale fp32 [ceil(M / rows_per_batch)][K] (nullable; row m of A is
+ * scaled by row m / rows_per_batch and rounded to fp16), c32 fp32 / c16 fp16 [M][N] ldc (at least one).  No split-K
+ * workspace.  The process options apply; *config_out (nullable) receives the instantiation that runs for exactly
+ * these arguments (a forced gemm_config that is inapplicable gives the automatic one).  K % 8, N % 4, lda % 8,
+ * ldw % 8, ldc % 4 == 0, act 0..4, 16-byte aligned base pointers, else MMF_EINVAL with nothing launched. */
+int mmf_gemm_f16_raw(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res32,
+                     const void* res16, int ldr, const float* ascale, int rows_per_batch, float* c32, void* c16,
+                     int ldc, int M, int N, int K, int act, int* config_out, void* stream);
 /* The lazy-LayerNorm producer (gemm.hip epi 2): c16 = fp16(A @ W^T + bias + res16), res16 / c16 fp16 [M][ldc] (the
  * same buffer: in place), and ln_out float2 [M][ceil(N / tn)] = per row and block of tn = mmf_gemm_ln_tn(M, N, K)
  * consecutive columns the (mean, sum of squared deviations) of the stored values.  K % 64 == 0, K >= 192,

@@ -803,7 +803,9 @@ extern "C" int mmf_debug_gemm_stamp(void* buf) {
 
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) return hipSuccess;
-  if ((a.K & 7) || (a.N & 3) || (a.lda & 7) || (a.ldw & 7) || (a.ldc & 3)) return hipErrorInvalidValue;
+  // (the epilogues read the residual as float4 / uint2 at m * ldr + n)
+  if ((a.K & 7) || (a.N & 3) || (a.lda & 7) || (a.ldw & 7) || (a.ldc & 3) || ((a.res32 || a.res16) && (a.ldr & 3)))
+    return hipErrorInvalidValue;
   if (a.epi != 0) {
     if (!epi_ok(a)) return hipErrorInvalidValue;
     return gemm_config(a) == 11 ? run_glds_epi<256, 256, 2, 4>(a, s) : run_glds_epi<256, 192, 4, 2>(a, s);

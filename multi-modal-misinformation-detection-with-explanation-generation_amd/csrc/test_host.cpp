@@ -1,7 +1,7 @@
 // Test-only entry points: the transformer towers' row kernels (norm.hip), the precise-mode kernels
 // (precise.hip), the one-query attention (attention.hip), the split-K skinny GEMM, the lazy-LN consumer and
 // producer epilogues and the QKV GEMM's attention epilogue (gemm.hip) on raw device operands (include/mmf_hip.h;
-// tests/test_gpu_transformer_kernels.py).  No handle.  Null, shape and alignment checks run on the host
+// tests/test_gpu_transformer_kernels.py), and the plain GEMM with independent strides (tests/test_gpu_gemm_kernels.py).  No handle.  Null, shape and alignment checks run on the host
 // before anything is launched; what a launcher does not support -- its own hipErrorInvalidValue
 // included -- is MMF_EINVAL with nothing written.
 #include "handle.h"
@@ -214,6 +214,30 @@ int mmf_gemm_f16_splitk(const void* A, int lda, const void* W, int ldw, const fl
   GemmArgs g = splitk_args(A, lda, W, ldw, bias, res32, res16, c32, c16, ldc, M, N, K, act);
   g.ws = ws;
   g.ws_elems = ws ? (size_t)ws_elems : 0;
+  return test_launch_rc(launch_gemm(g, (hipStream_t)stream), "gemm");
+}
+
+// the epilogue-0 GEMM with every operand and stride independent (tests/test_gpu_gemm_kernels.py): no split-K
+// workspace; *config_out = the instantiation launch_gemm runs for exactly these arguments
+int mmf_gemm_f16_raw(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res32,
+                     const void* res16, int ldr, const float* ascale, int rows_per_batch, float* c32, void* c16,
+                     int ldc, int M, int N, int K, int act, int* config_out, void* stream) {
+  if (!A || !W || (!c32 && !c16)) return fail(MMF_EINVAL, "null argument");
+  if (res32 && res16) return fail(MMF_EINVAL, "gemm: at most one of res32 / res16");
+  if (ascale && rows_per_batch <= 0) return fail(MMF_EINVAL, "rows_per_batch must be > 0 with ascale");
+  if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || act < 0 || act > 4)
+    return fail(MMF_EINVAL, "gemm: bad shape (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d act=%d)", M, N, K, lda, ldw, ldc, act);
+  if ((res32 || res16) && (ldr < N || (ldr & 3))) return fail(MMF_EINVAL, "gemm: bad residual stride %d (N=%d)", ldr, N);
+  if ((K & 7) || (N & 3) || (lda & 7) || (ldw & 7) || (ldc & 3))
+    return fail(MMF_EINVAL, "gemm: unsupported shape (N=%d K=%d lda=%d ldw=%d ldc=%d)", N, K, lda, ldw, ldc);
+  for (const void* p : {A, W, (const void*)bias, (const void*)res32, res16, (const void*)ascale, (const void*)c32,
+                        (const void*)c16})
+    if ((uintptr_t)p & 15) return fail(MMF_EINVAL, "gemm: operand %p is not 16-byte aligned", p);
+  GemmArgs g = splitk_args(A, lda, W, ldw, bias, res32, res16, c32, c16, ldc, M, N, K, act);
+  g.ldr = (res32 || res16) ? ldr : 0;
+  g.ascale = ascale;
+  g.rows_per_batch = rows_per_batch;
+  if (config_out) *config_out = gemm_config(g);
   return test_launch_rc(launch_gemm(g, (hipStream_t)stream), "gemm");
 }
 

@@ -110,6 +110,7 @@ SIGNATURES = {
     "mmf_gemm_splitk_factor": (_I, [_I, _I, _I, _I]),
     "mmf_gemm_f16_splitk": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_int64, _P]),
     "mmf_gemm_ln_tn": (_I, [_I, _I, _I]),
+    "mmf_gemm_f16_raw": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), _P]),
     "mmf_gemm_f16_ln_producer": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mmf_gemm_f16_ln_consumer": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "mmf_gemm_f16_attn": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -70,7 +70,7 @@ def _expand_dw(lib, xd, cin, wed, bed, wd, bd, B, H, C, k, stride, ct):
 
 
 def _expand_gemm(lib, xd, wed, bed, rows, cin, C):
-    """The 1x1 expand + SiLU as its own launch (mmf_gemm_f16_ex, act 3; tests/test_gpu_kernels.py covers it)."""
+    """The 1x1 expand + SiLU as its own launch (mmf_gemm_f16_ex, act 3; tests/test_gpu_gemm_kernels.py covers it)."""
     import mmf_amd.hip as hip
     E = torch.empty(rows, C, device="cuda", dtype=torch.float16)
     hip.check(lib.mmf_gemm_f16_ex(xd.data_ptr(), cin, wed.data_ptr(), cin, bed.data_ptr(), None, None, 0, E.data_ptr(),
