@@ -648,6 +648,53 @@ int mmf_gemm_f16_ln_consumer(const void* A, int lda, const void* W, int ldw, con
 int mmf_gemm_f16_attn(const void* A, int lda, const void* W, int ldw, const float* bias, const int32_t* amask, void* ctx,
                       int ldc, int M, int N, int K, void* stream);
 
+/* Low-level ops exported for unit tests of the closing fp32 kernels (csrc/misc.hip; tests/test_gpu_misc_kernels.py)
+ * and of the vault's stages (csrc/vault.hip; tests/test_gpu_vault_kernels.py).  No handle; every pointer is a device
+ * pointer; work is enqueued on `stream`.  Null, shape, stride and alignment checks run on the host; what a launcher
+ * does not support is MMF_EINVAL with nothing launched.
+ *
+ * text_heads: the two Linear(768,256)-ReLU-Linear(256,2) heads on rows x[b * row_stride .. + 768) (row_stride >= 768).
+ *   w1a_t / w1m_t are the first layers TRANSPOSED, [768][256], as the kernel reads them; b1 [256], w2 [2][256], b2 [2].
+ *   ai_logits / mi_logits [B][2] and scores (scores[b * score_stride + 0] = softmax(ai)[1], [+ 1] = softmax(misinfo)[1],
+ *   score_stride >= 2) are nullable, not all three.  ovf (nullable, int32 [B]): a row with ovf[b] != 0 gets NaN.
+ * text_cls_rows: out [B][768] = the same rows, NaN where ovf[b] != 0; row_stride % 4 == 0, x and out 16-byte aligned.
+ * fusion_raw: the FusionJudge MLP 5 -> 64 -> 32 -> 2 with ReLUs on x5 [B][5], weights as PyTorch stores them (w0
+ *   [64][5], w3 [32][64], w5 [2][32]) -> probs [B][2] = softmax, verdict = probs[1] > 0.5, conf = the verdict's
+ *   probability, rule = the explanation cascade on x5 (verdict, conf, rule nullable).
+ * rowdot: out[b * ostride] = dot(a[b], c[b]) over C columns.
+ * mixed_finish_raw: mmf_analyze_mixed's last kernel; the arguments are csrc/kernels.h MixedFinishArgs field by field.
+ * vault_sims: S [B][N] = q [B][D] . v [N][D]^T, each element one fp32 fma chain over k = 0 .. D - 1; D % 64 == 0, q, v
+ *   and S 16-byte aligned; ref 0 = the fp32-MFMA kernel, 1 = the VALU kernel it is bit-identical to.
+ * vault_topk: the top k of each row of a caller-supplied S [B][N] (value descending, NaN first, ties by descending
+ *   index; slots past N hold (-inf, -1)) -> sims / idx [B][k], disc[b * disc_stride] = the top-1 of a hit (> thresh,
+ *   not NaN) else 0, tsim[b] = dot(temb[b], title[top-1]) over D columns on a hit with both present, else 0; every
+ *   output nullable, not all.  k <= 8 runs the register kernels, k > 8 (or ref = 1 with N <= 16384) the LDS sort,
+ *   which needs max(N, k) <= 16384.
+ * vault_sort_cand: the final ranking of cs / cidx [chunks][B][k] per-chunk results (chunk-local indices, -1 = an empty
+ *   slot; global index = chunk * chunk_rows + local), chunks * k <= 16384, with the same outputs. */
+int mmf_text_heads_f32(const float* x, int row_stride, const float* w1a_t, const float* b1a, const float* w2a,
+                       const float* b2a, const float* w1m_t, const float* b1m, const float* w2m, const float* b2m,
+                       float* ai_logits, float* mi_logits, float* scores, int score_stride, const int32_t* ovf, int B,
+                       void* stream);
+int mmf_text_cls_rows_f32(const float* x, int row_stride, const int32_t* ovf, float* out, int B, void* stream);
+int mmf_fusion_raw_f32(const float* x5, const float* w0, const float* b0, const float* w3, const float* b3,
+                       const float* w5, const float* b5, float* probs, int32_t* verdict, float* conf, int32_t* rule,
+                       int B, void* stream);
+int mmf_rowdot_f32(const float* a, const float* c, float* out, int ostride, int B, int C, void* stream);
+int mmf_mixed_finish_raw(const int32_t* row_map, int B, int nT, int nI, int nC, const float* text2,
+                         const float* deepfake, const float* v_emb, const float* t_emb, const float* c_sims,
+                         const int32_t* c_idx, const float* c_disc, const float* title, float thresh, const float* w0,
+                         const float* b0, const float* w3, const float* b3, const float* w5, const float* b5,
+                         float* scores5, float* text_sim, float* probs, int32_t* verdict, float* conf, int32_t* rule,
+                         float* top_sims, int32_t* top_idx, void* stream);
+int mmf_vault_sims_f32(const float* q, const float* v, float* S, int B, int N, int D, int ref, void* stream);
+int mmf_vault_topk_f32(const float* S, int B, int N, int k, float thresh, float* sims, int32_t* idx, float* disc,
+                       int disc_stride, const float* temb, const float* title, int D, float* tsim, int ref,
+                       void* stream);
+int mmf_vault_sort_cand_f32(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
+                            float thresh, float* sims, int32_t* idx, float* disc, int disc_stride, const float* temb,
+                            const float* title, int D, float* tsim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

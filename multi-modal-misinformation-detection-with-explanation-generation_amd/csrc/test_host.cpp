@@ -1,9 +1,11 @@
 // Test-only entry points: the transformer towers' row kernels (norm.hip), the precise-mode kernels
 // (precise.hip), the one-query attention (attention.hip), the split-K skinny GEMM, the lazy-LN consumer and
 // producer epilogues and the QKV GEMM's attention epilogue (gemm.hip) on raw device operands (include/mmf_hip.h;
-// tests/test_gpu_transformer_kernels.py), and the plain GEMM with independent strides (tests/test_gpu_gemm_kernels.py).  No handle.  Null, shape and alignment checks run on the host
-// before anything is launched; what a launcher does not support -- its own hipErrorInvalidValue
-// included -- is MMF_EINVAL with nothing written.
+// tests/test_gpu_transformer_kernels.py), the plain GEMM with independent strides (tests/test_gpu_gemm_kernels.py),
+// the closing fp32 kernels (misc.hip; tests/test_gpu_misc_kernels.py) and the vault's similarity, top-k and
+// candidate-sort stages (vault.hip; tests/test_gpu_vault_kernels.py).  No handle.  Null, shape and alignment
+// checks run on the host before anything is launched; what a launcher does not support -- its own
+// hipErrorInvalidValue included -- is MMF_EINVAL with nothing written.
 #include "handle.h"
 
 namespace {
@@ -292,6 +294,132 @@ int mmf_gemm_f16_ln_producer(const void* A, int lda, const void* W, int ldw, con
   if (!gemm_epi_ok(g))
     return fail(MMF_EINVAL, "lazy-LN producer epilogue not applicable (M=%d N=%d K=%d ldc=%d)", M, N, K, ldc);
   return test_launch_rc(launch_gemm(g, (hipStream_t)stream), "gemm (lazy-LN producer)");
+}
+
+}  // extern "C"
+
+// ---- the closing fp32 kernels (misc.hip) and the vault's stages (vault.hip) on raw operands
+// (tests/test_gpu_misc_kernels.py, tests/test_gpu_vault_kernels.py) ----
+namespace {
+
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+VaultOut vault_out(float thresh, float* sims, int32_t* idx, float* disc, int disc_stride, const float* temb,
+                   const float* title, int D, float* tsim) {
+  VaultOut o{};
+  o.thresh = thresh;
+  o.sims = sims;
+  o.idx = idx;
+  o.disc = disc;
+  o.disc_stride = disc_stride;
+  o.temb = temb;
+  o.title = title;
+  o.D = D;
+  o.tsim = tsim;
+  return o;
+}
+
+// what every VaultOut needs whichever kernel fills it
+bool vault_out_ok(const VaultOut& o) {
+  if (!o.sims && !o.idx && !o.disc && !o.tsim) return false;
+  if (o.disc && o.disc_stride < 1) return false;
+  if (o.tsim && o.temb && o.title && o.D < 1) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmf_text_heads_f32(const float* x, int row_stride, const float* w1a_t, const float* b1a, const float* w2a,
+                       const float* b2a, const float* w1m_t, const float* b1m, const float* w2m, const float* b2m,
+                       float* ai_logits, float* mi_logits, float* scores, int score_stride, const int32_t* ovf, int B,
+                       void* stream) {
+  if (!x || !w1a_t || !b1a || !w2a || !b2a || !w1m_t || !b1m || !w2m || !b2m) return fail(MMF_EINVAL, "null argument");
+  if (!ai_logits && !mi_logits && !scores) return fail(MMF_EINVAL, "text_heads: no output");
+  if (B <= 0 || row_stride < 768 || (scores && score_stride < 2))
+    return fail(MMF_EINVAL, "text_heads: bad shape (B=%d row_stride=%d score_stride=%d)", B, row_stride, score_stride);
+  return test_launch_rc(launch_text_heads(x, row_stride, w1a_t, b1a, w2a, b2a, w1m_t, b1m, w2m, b2m, ai_logits,
+                                          mi_logits, scores, score_stride, B, (hipStream_t)stream, ovf),
+                        "text_heads");
+}
+
+int mmf_text_cls_rows_f32(const float* x, int row_stride, const int32_t* ovf, float* out, int B, void* stream) {
+  if (!x || !out) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || row_stride < 768 || (row_stride & 3) || !al16(x) || !al16(out))
+    return fail(MMF_EINVAL, "text_cls_rows: bad shape or alignment (B=%d row_stride=%d)", B, row_stride);
+  return test_launch_rc(launch_text_cls_rows(x, row_stride, ovf, out, B, (hipStream_t)stream), "text_cls_rows");
+}
+
+int mmf_fusion_raw_f32(const float* x5, const float* w0, const float* b0, const float* w3, const float* b3,
+                       const float* w5, const float* b5, float* probs, int32_t* verdict, float* conf, int32_t* rule,
+                       int B, void* stream) {
+  if (!x5 || !w0 || !b0 || !w3 || !b3 || !w5 || !b5 || !probs) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0) return fail(MMF_EINVAL, "fusion: bad batch %d", B);
+  return test_launch_rc(launch_fusion(x5, w0, b0, w3, b3, w5, b5, probs, verdict, conf, rule, B, (hipStream_t)stream),
+                        "fusion");
+}
+
+int mmf_rowdot_f32(const float* a, const float* c, float* out, int ostride, int B, int C, void* stream) {
+  if (!a || !c || !out) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || C <= 0 || ostride < 1) return fail(MMF_EINVAL, "rowdot: bad shape (B=%d C=%d ostride=%d)", B, C, ostride);
+  return test_launch_rc(launch_rowdot(a, c, out, ostride, B, C, (hipStream_t)stream), "rowdot");
+}
+
+int mmf_mixed_finish_raw(const int32_t* row_map, int B, int nT, int nI, int nC, const float* text2,
+                         const float* deepfake, const float* v_emb, const float* t_emb, const float* c_sims,
+                         const int32_t* c_idx, const float* c_disc, const float* title, float thresh, const float* w0,
+                         const float* b0, const float* w3, const float* b3, const float* w5, const float* b5,
+                         float* scores5, float* text_sim, float* probs, int32_t* verdict, float* conf, int32_t* rule,
+                         float* top_sims, int32_t* top_idx, void* stream) {
+  if (nT < 0 || nI < 0 || nC < 0) return fail(MMF_EINVAL, "mixed_finish: bad list sizes (nT=%d nI=%d nC=%d)", nT, nI, nC);
+  MixedFinishArgs a{};
+  a.row_map = row_map;
+  a.B = B; a.nT = nT; a.nI = nI; a.nC = nC;
+  a.text2 = text2;
+  a.deepfake = deepfake;
+  a.v_emb = v_emb;
+  a.t_emb = t_emb;
+  a.c_sims = c_sims;
+  a.c_idx = c_idx;
+  a.c_disc = c_disc;
+  a.title = title;
+  a.thresh = thresh;
+  a.w0 = w0; a.b0 = b0; a.w3 = w3; a.b3 = b3; a.w5 = w5; a.b5 = b5;
+  a.scores5 = scores5; a.text_sim = text_sim; a.probs = probs;
+  a.verdict = verdict; a.conf = conf; a.rule = rule;
+  a.top_sims = top_sims; a.top_idx = top_idx;
+  return test_launch_rc(launch_mixed_finish(a, (hipStream_t)stream), "mixed_finish");
+}
+
+int mmf_vault_sims_f32(const float* q, const float* v, float* S, int B, int N, int D, int ref, void* stream) {
+  if (!q || !v || !S) return fail(MMF_EINVAL, "null argument");
+  if (B <= 0 || N <= 0 || D <= 0 || (D & 63)) return fail(MMF_EINVAL, "vault_sims: bad shape (B=%d N=%d D=%d)", B, N, D);
+  if (!al16(q) || !al16(v) || !al16(S)) return fail(MMF_EINVAL, "vault_sims: operands must be 16-byte aligned");
+  return test_launch_rc(launch_vault_sims(q, v, S, B, N, D, (hipStream_t)stream, ref), "vault_sims");
+}
+
+int mmf_vault_topk_f32(const float* S, int B, int N, int k, float thresh, float* sims, int32_t* idx, float* disc,
+                       int disc_stride, const float* temb, const float* title, int D, float* tsim, int ref,
+                       void* stream) {
+  if (!S) return fail(MMF_EINVAL, "null argument");
+  const VaultOut o = vault_out(thresh, sims, idx, disc, disc_stride, temb, title, D, tsim);
+  if (B <= 0 || N <= 0 || k <= 0 || !vault_out_ok(o))
+    return fail(MMF_EINVAL, "vault_topk: bad shape or no output (B=%d N=%d k=%d disc_stride=%d D=%d)", B, N, k,
+                disc_stride, D);
+  return test_launch_rc(launch_vault_topk(S, B, N, k, o, (hipStream_t)stream, ref), "vault_topk");
+}
+
+int mmf_vault_sort_cand_f32(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
+                            float thresh, float* sims, int32_t* idx, float* disc, int disc_stride, const float* temb,
+                            const float* title, int D, float* tsim, void* stream) {
+  if (!cs || !cidx) return fail(MMF_EINVAL, "null argument");
+  const VaultOut o = vault_out(thresh, sims, idx, disc, disc_stride, temb, title, D, tsim);
+  if (B <= 0 || chunks <= 0 || chunk_rows <= 0 || k <= 0 || (long long)chunks * k > 16384 || !vault_out_ok(o))
+    return fail(MMF_EINVAL, "vault_sort_cand: bad shape or no output (chunks=%d chunk_rows=%d B=%d k=%d)", chunks,
+                chunk_rows, B, k);
+  return test_launch_rc(launch_vault_sort_cand(cs, cidx, chunks, chunk_rows, B, k, o, (hipStream_t)stream),
+                        "vault_sort_cand");
 }
 
 }  // extern "C"

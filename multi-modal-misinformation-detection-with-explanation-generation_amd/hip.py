@@ -114,6 +114,16 @@ SIGNATURES = {
     "mmf_gemm_f16_ln_producer": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mmf_gemm_f16_ln_consumer": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "mmf_gemm_f16_attn": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    # the closing fp32 kernels and the vault's stages on raw operands (csrc/test_host.cpp)
+    "mmf_text_heads_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "mmf_text_cls_rows_f32": (_I, [_P, _I, _P, _P, _I, _P]),
+    "mmf_fusion_raw_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mmf_rowdot_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "mmf_mixed_finish_raw": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmf_vault_sims_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_vault_topk_f32": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P]),
+    "mmf_vault_sort_cand_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 
 _lib = None
@@ -131,6 +141,13 @@ def load(path: str | None = None):
     p = path or os.environ.get("MMF_HIP_LIB", LIB_PATH)
     if not os.path.exists(p):
         raise MMFError(f"libmmf_hip.so not found at {p}; build it with `make -C {PKG_DIR}/csrc`")
+    # torch before the library, for every caller: its wheel preloads its own bundled HIP runtime by path; loaded
+    # after libmmf_hip.so has pulled in the system one, the process holds two runtimes and the second to initialise
+    # finds no device (mmf_create fails).  A process without torch has no second runtime to meet.
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass
     try:
         lib = ctypes.CDLL(p)
     except OSError as e:

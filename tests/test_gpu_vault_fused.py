@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.vault_refs import rank as _rank  # the project's ranking in numpy
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
@@ -23,14 +25,6 @@ def _bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
     if a.dtype == torch.float32:
         a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
     return bool(torch.equal(a, b))
-
-
-def _rank(s: np.ndarray, k: int):
-    """The project's ranking of one row of similarities: value descending, NaN first, exact ties by
-    descending index (what np.argsort(s)[::-1] gives with a stable sort)."""
-    key = np.where(np.isnan(s), np.inf, s)
-    order = np.lexsort((-np.arange(len(s)), -key))[:k]
-    return s[order], order
 
 
 @pytest.fixture(scope="module")
