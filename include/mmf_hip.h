@@ -408,6 +408,8 @@ const char* mmf_profile_kind_name(int kind);
  *   "diag_skip"      0: diagnostic bitmask of towers mmf_analyze_batch leaves out (2 EfficientNet,
  *                       4 CLIP text, 8 ViT, ...; measurement only)
  *   "qkv_attn"       1: RoBERTa L = 128: attention in the QKV GEMM's epilogue
+ *   "clip_qkv_attn"  1: CLIP towers (lazy LN, L <= 128): attention in the QKV consumer GEMM's epilogue
+ *                       (bit-identical to 0; 2 = ViT only, 4 = text tower only)
  *   "vault_ref"      0: diagnostic: vault similarities on the VALU kernel, top-k by full sort (the
  *                       reference kernels the production MFMA / register top-k kernels equal bit for bit)
  *   "vault_fused"    2: vault search without the [B, N] similarity matrix (fused similarity + top-k
@@ -647,6 +649,15 @@ int mmf_gemm_f16_ln_consumer(const void* A, int lda, const void* W, int ldw, con
  * K % 64 == 0, K >= 192, ldc >= N / 3, else MMF_EINVAL. */
 int mmf_gemm_f16_attn(const void* A, int lda, const void* W, int ldw, const float* bias, const int32_t* amask, void* ctx,
                       int ldc, int M, int N, int K, void* stream);
+/* The lazy-LayerNorm consumer with the attention of its rows in the epilogue (gemm.hip epi 5): the operands of
+ * mmf_gemm_f16_ln_consumer with W / ln_u / bias rows interleaved per head as for mmf_gemm_f16_attn, A = sequences of L
+ * rows (16 <= L <= 128, M % L == 0), amask int32 [M / L][L] (1 keep) or NULL, causal 0 / 1 -> ctx fp16 [M][ldc], head
+ * h at columns 64 h: bit-identical to mmf_gemm_f16_ln_consumer (256 x 192 tiles) on the same operands, de-interleaved,
+ * followed by mmf_attention_f16.  N % 192 == 0, K % 64 == 0, K >= 192, P <= 8, P * tn >= K, ldc >= N / 3, else
+ * MMF_EINVAL with nothing written. */
+int mmf_gemm_f16_ln_attn(const void* A, int lda, const void* W, int ldw, const float* bias, const void* ln_in, int P,
+                         int tn, const float* ln_u, float eps, const int32_t* amask, int L, int causal, void* ctx,
+                         int ldc, int M, int N, int K, void* stream);
 
 /* Low-level ops exported for unit tests of the closing fp32 kernels (csrc/misc.hip; tests/test_gpu_misc_kernels.py)
  * and of the vault's stages (csrc/vault.hip; tests/test_gpu_vault_kernels.py).  No handle; every pointer is a device

@@ -51,6 +51,7 @@ const OptName kOptNames[] = {
     {"pw32_mfma", &Options::pw32_mfma, "MMF_PW32_MFMA"},
     {"effnet_chunks", &Options::effnet_chunks, "MMF_EFFNET_CHUNKS"}, {"dw_cw32", &Options::dw_cw32, "MMF_DW_CW32"},
     {"diag_skip", &Options::diag_skip, "MMF_DIAG_SKIP"}, {"qkv_attn", &Options::qkv_attn, "MMF_QKV_ATTN"},
+    {"clip_qkv_attn", &Options::clip_qkv_attn, "MMF_CLIP_QKV_ATTN"},
     {"vault_ref", &Options::vault_ref, "MMF_VAULT_REF"}, {"vault_fused", &Options::vault_fused, "MMF_VAULT_FUSED"},
     {"mt_enqueue", &Options::mt_enqueue, "MMF_MT_ENQUEUE"}, {"last_q1", &Options::last_q1, "MMF_LAST_Q1"},
     {"after_text", &Options::after_text, "MMF_AFTER_TEXT"},

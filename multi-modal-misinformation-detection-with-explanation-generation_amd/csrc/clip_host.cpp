@@ -67,21 +67,24 @@ struct ClipEnc {
   bool lazy;
   LnStats cur;  // lazy LN: partials of the current stream
   int sti;      // which of the two partial buffers holds them
+  bool qkv_attn;  // lazy LN: attention in the QKV consumer's epilogue (option clip_qkv_attn)
 };
+// option clip_qkv_attn for a tower: 1 = both, else a bitmask (2 ViT, 4 text tower)
+bool clip_qkv_attn_on(const mmf_handle* h, int bit) { return h->opt.clip_qkv_attn == 1 || (h->opt.clip_qkv_attn & bit); }
 
 ClipEnc vit_enc(mmf_handle* h, int B) {
   Workspace& w = h->ws;
   const int M = B * 50;
   return ClipEnc{h->v_layers, 768, 3072, 12, w.v_x, h->opt.clip_res16 ? reinterpret_cast<f16_t*>(w.v_x) : nullptr,
                  w.v_xb, w.v_qkv, w.v_ctx, w.v_h, nullptr, 0, B, 50, M, nullptr, w.v_xc, w.v_ctxc, w.sk_vit,
-                 w.sk_elems, w.v_st, clip_lazy(h, M), LnStats{w.v_st[0], 1, 768}, 0};
+                 w.sk_elems, w.v_st, clip_lazy(h, M), LnStats{w.v_st[0], 1, 768}, 0, clip_qkv_attn_on(h, 2)};
 }
 ClipEnc text_enc(mmf_handle* h, const int32_t* mask, int B, int L) {
   Workspace& w = h->ws;
   const int M = B * L;
   return ClipEnc{h->t_layers, 512, 2048, 8, w.t_x, h->opt.clip_res16 ? reinterpret_cast<f16_t*>(w.t_x) : nullptr,
                  w.t_xb, w.t_qkv, w.t_ctx, w.t_h, mask, 1, B, L, M, w.t_eos, w.t_xc, w.t_ctxc, w.sk_ctext,
-                 w.sk_elems, w.t_st, clip_lazy(h, M), LnStats{w.t_st[0], 1, 512}, 0};
+                 w.sk_elems, w.t_st, clip_lazy(h, M), LnStats{w.t_st[0], 1, 512}, 0, clip_qkv_attn_on(h, 4)};
 }
 
 // the four GEMMs of a lazy-LN layer (not the last): QKV and FFN-1 read the raw stream with LN1 / LN2
@@ -90,6 +93,19 @@ GemmArgs lazy_qkv(ClipEnc& E, int i) {
   const EncLayer& Ly = E.layers[i];
   GemmArgs g = ln_consumer(E.x16, E.H, Ly.qkv_f, Ly.qkv_u, E.cur, E.M);
   g.c16 = E.qkv;
+  return g;
+}
+// the same consumer on the per-head interleaved folded weights with the attention of its rows in the
+// epilogue (gemm.hip epi 5): ctx straight from the stream, qkv never stored
+GemmArgs lazy_qkv_attn(ClipEnc& E, int i) {
+  const EncLayer& Ly = E.layers[i];
+  GemmArgs g = ln_consumer(E.x16, E.H, Ly.qkv_fh, Ly.qkv_uh, E.cur, E.M);
+  g.epi = 5;
+  g.c16 = E.ctx;
+  g.ldc = E.H;
+  g.amask = E.mask;
+  g.att_L = E.L;
+  g.att_causal = E.causal;
   return g;
 }
 GemmArgs lazy_producer(mmf_handle* h, ClipEnc& E, const f16_t* A, int lda, const Lin16& l) {
@@ -143,10 +159,19 @@ int run_clip_encoder(mmf_handle* h, ClipEnc& E, int i0, int i1, hipStream_t s) {
                                    B, L, E.heads, s));
       }
     } else {
-      g = E.lazy ? lazy_qkv(E, i) : with_ws(gemm_args(E.xb, H, Ly.qkv, M), E.skws, E.sk_elems);
-      if (!E.lazy) g.c16 = E.qkv;
-      CHK(gemm(h, g, s));
-      CHK(attn(h, E.qkv, 3 * H, E.mask, E.ctx, H, B, L, E.heads, E.causal, s));
+      bool fused = false;
+      if (E.lazy && E.qkv_attn && L <= 128) {
+        g = lazy_qkv_attn(E, i);
+        fused = gemm_epi_ok(g);
+      }
+      if (fused) {
+        CHK(gemm(h, g, s));
+      } else {
+        g = E.lazy ? lazy_qkv(E, i) : with_ws(gemm_args(E.xb, H, Ly.qkv, M), E.skws, E.sk_elems);
+        if (!E.lazy) g.c16 = E.qkv;
+        CHK(gemm(h, g, s));
+        CHK(attn(h, E.qkv, 3 * H, E.mask, E.ctx, H, B, L, E.heads, E.causal, s));
+      }
     }
     if (i == 11) {
       if (!(h->opt.last_q1 & 2))

@@ -456,6 +456,118 @@ MMF_DEV void attention_epilogue(const GemmArgs& g, const f32x4 (&acc)[NI][MI], c
   __syncthreads();  // the window is the next tile's second-slab stage
 }
 
+// Attention epilogue for any L in 16 .. 128 (EPI 5 / 6: the CLIP towers' lazy-LN QKV consumers, option
+// clip_qkv_attn; L = 50 / LK 64 for the ViT, L = 77 / LK 96 causal for the text tower).  The tile's 256 rows
+// are S = 256 / L whole sequences (+ 256 - S L rows that are computed and dropped); win holds q | k | v of
+// head `head` as three [256 tile rows][64] fp16 images in attention.hip's swizzle.  One unit of work is
+// attention_kernel<LK, CAUSAL>'s arithmetic for one (sequence, 16-query tile), same operations in the same
+// order, so ctx is bit-identical to the consumer GEMM + attention_kernel pair; the units go round the 8 waves.
+// With S LK > 256 the sequences cannot each have LK rows of their own, so they stay packed and every
+// per-lane row address of a key or query >= L is redirected to zrow, 128 B of zeros: the stand-alone kernel
+// reads zeros there, and a neighbour's rows must not be read (P = 0 for those keys, but 0 * inf is NaN).
+// kbias: [S][LK] floats (S LK <= 512: L >= 16).
+template <int LK, bool CAUSAL>
+MMF_DEV void attention_epilogue_seq(const GemmArgs& g, const f16_t* win, const f16_t* zrow, float* kbias, int m0,
+                                    int head, int M, int S, int wave, int tid_) {
+  // the lane index and L are made opaque here, once per tile: otherwise hipcc hoists every lane- and
+  // L-dependent address and predicate of the four LK variants to the kernel's start and carries them
+  // through the K loop (measured: 256 VGPRs and 28 B of scratch; with this 0 scratch)
+  int tid = tid_, L = g.att_L;
+  asm volatile("" : "+v"(tid), "+s"(L));
+  const int fr = tid & 15, fg = (tid >> 4) & 3;
+  const f16_t* Qs = win;
+  const f16_t* Ks = win + 16384;
+  const f16_t* Vs = win + 32768;
+  if (tid < S * LK) {  // key bias of sequence sq, key j (a sequence past M: never read)
+    const int sq = tid / LK, j = tid - sq * LK, m = m0 + sq * L + j;
+    const bool keep = j < L && m < M && (!g.amask || g.amask[(size_t)min(m, M - 1)] != 0);
+    kbias[tid] = keep ? 0.f : -INFINITY;
+  }
+  __syncthreads();
+  constexpr int NKT = LK / 16;
+  const int nqt = (L + 15) >> 4;
+  const int nseq = min(S, (M - m0) / L);  // whole sequences of this panel (M = B L)
+#pragma unroll 1
+  for (int unit = wave; unit < nseq * nqt; unit += 8) {
+    const int sq = unit / nqt, qt = unit - sq * nqt, r0 = sq * L;
+    const float* kb_s = kbias + sq * LK;
+    const int qq = qt * 16 + fr;
+    f16x8 qf[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+      qf[ks] = as_f16x8(*reinterpret_cast<const uint4*>(qq < L ? Qs + swz(r0 + qq, ks * 4 + fg) : zrow + (ks * 4 + fg) * 8));
+    f32x4 s[NKT];
+#pragma unroll
+    for (int j = 0; j < NKT; ++j) {
+      s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int key = j * 16 + fr, kc = ks * 4 + fg;
+        const f16x8 kf = as_f16x8(*reinterpret_cast<const uint4*>(key < L ? Ks + swz(r0 + key, kc) : zrow + kc * 8));
+        s[j] = mfma16x16x32(kf, qf[ks], s[j]);
+      }
+    }
+    constexpr float kScaleLog2e = 0.125f * 1.44269504088896341f;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NKT; ++j) {
+      const float4 kb = *reinterpret_cast<const float4*>(kb_s + j * 16 + fg * 4);
+      const float kbr[4] = {kb.x, kb.y, kb.z, kb.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = fmaf(s[j][r], kScaleLog2e, kbr[r]);
+        if (CAUSAL && j * 16 + fg * 4 + r > qq) v = -INFINITY;
+        s[j][r] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (mx == -INFINITY) mx = 0.f;  // every key masked: all exponentials 0, sum 0, output 0
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < NKT; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = __builtin_amdgcn_exp2f(s[j][r] - mx);
+        s[j][r] = e;
+        sum += e;
+      }
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = sum == 0.f ? 0.f : 1.0f / sum;
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < LK / 32; ++kb) {
+      const uint4 pk = make_uint4(pack2h(s[2 * kb][0], s[2 * kb][1]), pack2h(s[2 * kb][2], s[2 * kb][3]),
+                                  pack2h(s[2 * kb + 1][0], s[2 * kb + 1][1]), pack2h(s[2 * kb + 1][2], s[2 * kb + 1][3]));
+      const f16x8 pf = as_f16x8(pk);
+      const int key0 = kb * 32 + fg * 4 + (fr >> 2), p = fr & 3;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const int c = dt * 2 + (p >> 1), e = (p & 1) * 4;
+        const f16_t* plo = key0 < L ? Vs + swz(r0 + key0, c) + e : zrow + c * 8 + e;
+        const f16_t* phi = key0 + 16 < L ? Vs + swz(r0 + key0 + 16, c) + e : zrow + c * 8 + e;
+        const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)plo);
+        const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)phi);
+        const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+        o[dt] = mfma16x16x32(as_f16x8(make_uint4(l2.x, l2.y, h2.x, h2.y)), pf, o[dt]);
+      }
+    }
+    if (qq < L) {
+      f16_t* dst = g.c16 + (size_t)(m0 + r0 + qq) * g.ldc + head * 64 + fg * 4;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        *reinterpret_cast<uint2*>(dst + dt * 16) =
+            make_uint2(pack2h(o[dt][0] * inv, o[dt][1] * inv), pack2h(o[dt][2] * inv, o[dt][3] * inv));
+    }
+  }
+  __syncthreads();  // the window is the next tile's second-slab stage
+}
+
 // Diagnostic build only (-DMMF_GEMM_STAMP, tools/gemm_stamps.py): per-workgroup
 // phase stamps of the persistent kernel into a buffer of its own ([workgroup][kGStampSlots]: 0 / 1 =
 // s_memrealtime at start / end, 2 = number of stamps, 3.. = s_memtime at each tile's start, after its
@@ -571,7 +683,9 @@ hipError_t run_glds(const GemmArgs& a, hipStream_t s) {
 // lazy-LN / attention epilogues (pipelined 256-row tiles only)
 template <int BM, int BN, int WGM, int WGN>
 hipError_t run_glds_epi(const GemmArgs& a, hipStream_t s) {
-  const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
+  // (epi 5: a row panel holds the S = 256 / L whole sequences of L rows that fit a tile)
+  const int seqs = a.epi == 5 ? BM / a.att_L : 0;
+  const int tilesM = a.epi == 5 ? (a.M / a.att_L + seqs - 1) / seqs : (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
   const int tiles = tilesM * tilesN;
   const int grid = tiles < 256 ? tiles : 256;
   const dim3 blk(64 * WGM * WGN);
@@ -595,6 +709,11 @@ hipError_t run_glds_epi(const GemmArgs& a, hipStream_t s) {
     if constexpr (BN == 192) MMF_EPI_CASE(2, ACT_NONE);
   } else if (a.epi == 3) {
     if constexpr (BN == 192) MMF_EPI_CASE(3, ACT_NONE);
+  } else if (a.epi == 5) {
+    if constexpr (BN == 192) {
+      if (a.att_causal) MMF_EPI_CASE(6, ACT_NONE);
+      else MMF_EPI_CASE(5, ACT_NONE);
+    }
   } else {
     return hipErrorInvalidValue;
   }
@@ -742,7 +861,7 @@ static int glds_pick(const GemmArgs& a, bool with_128) {
 int gemm_config(const GemmArgs& a) {
   // producers: 256x192 tiles, 96-column partials (P = ceil(N / 96) <= kLnPMax), decided from N
   // only, so a row's statistics (and so its result) do not depend on the batch it runs in
-  if (a.epi == 2 || a.epi == 3) return 10;
+  if (a.epi == 2 || a.epi == 3 || a.epi == 5) return 10;
   const int f = forced_config(a);
   if (a.epi == 1 || a.epi == 4) return (f == 10 || f == 11) ? f : glds_pick(a, false);
   if (f >= 0) return f;
@@ -777,6 +896,10 @@ static bool epi_ok(const GemmArgs& a) {
   if (a.epi == 3)  // whole 128-row sequences, whole heads (192 = q | k | v columns of one head)
     return a.c16 && !a.c32 && !a.res16 && !a.res32 && a.bias && a.act == ACT_NONE && a.N % 192 == 0 &&
            a.M % 128 == 0 && a.ldc >= a.N / 3;
+  if (a.epi == 5)  // the consumer's operands, whole heads, whole sequences of 16 .. 128 rows (S LK <= 512 key-bias slots)
+    return a.ln_in && a.ln_u && a.bias && a.c16 && !a.c32 && !a.res16 && !a.res32 && a.act == ACT_NONE && a.ln_in_P >= 1 &&
+           a.ln_in_P <= kLnPMax && a.ln_in_tn > 0 && (long)a.ln_in_P * a.ln_in_tn >= a.K && a.N % 192 == 0 &&
+           a.att_L >= 16 && a.att_L <= 128 && a.M % a.att_L == 0 && a.ldc >= a.N / 3;
   if (a.epi == 4)
     return a.c16 && !a.c32 && !a.res16 && !a.res32 && a.bias && a.act == ACT_GELU && a.N % 8 == 0 &&
            a.ldc >= (a.split_lo ? 3 * a.N : a.N) && (size_t)(a.M + 256) * a.ldc * 2 < ((size_t)1 << 31);

@@ -13,11 +13,15 @@
   static_assert(NW == 8 && BM == 256, "8 waves, 256-row tiles");
   // EPI 3 (attention epilogue, RoBERTa QKV): a 40 KB gap between the two stages, so that the stage
   // the last K-step freed plus the gap hold q (32 KB) and k | v (64 KB) of the tile's two sequences
-  constexpr bool ATT = EPI == 3;
+  // EPI 5 / 6 (CLIP QKV, 6 = causal): the lazy-LN consumer with the attention of the tile's S = 256 / L
+  // whole sequences in its epilogue (attention_epilogue_seq); row panel tm starts at row tm * S * L
+  constexpr bool ATTG = EPI == 5 || EPI == 6;
+  constexpr bool ATT = EPI == 3 || ATTG;
+  constexpr bool LNC = EPI == 1 || ATTG;  // lazy-LN consumer: (mean, rstd) from partials, u and c through LDS
   static_assert(!ATT || (BM == 256 && BN == 192 && WGM == 4 && WGN == 2 && PIPE2), "attention epilogue: 256x192");
   constexpr int XGAP = ATT ? 20480 : 0;  // f16 elements
   constexpr int SOFF = STAGE + XGAP;     // stage 1's offset
-  constexpr bool ROWST = EPI == 1;  // reads row statistics
+  constexpr bool ROWST = LNC;  // reads row statistics
   static_assert(EPI == 0 || BM == 256, "lazy-LN epilogues assume 256-row tiles");
   // ONE __shared__ object, carved: the operand stages | row partials | column vectors | row stats.
   // With a second LDS object in the kernel, hipcc's wait-count pass gives every LDS access alias
@@ -27,13 +31,20 @@
   // column vectors of a consumer tile: u | bias (bias through LDS frees the 4*NI bias registers the
   // plain path holds across the K loop); ATT: the key mask bias
   constexpr int kBiasCol = 256;
-  constexpr int kStageB = (2 * STAGE + XGAP) * 2, kRowsB = ROWST ? BM * kLnPMax * 8 : 0;
+  // ATTG byte budget (163,840 available): stages 2 x 57,344 + gap 40,960 = 155,648 | u, c 2,048 | row
+  // stats 2,048 | key bias 2,048 | zero row 128 = 161,920.  The 16 KB of row partials alias the head of the
+  // gap: they are consumed at the third K-step, the gap is written only by the epilogue.
+  constexpr int kStageB = (2 * STAGE + XGAP) * 2, kRowsB = (ROWST && !ATTG) ? BM * kLnPMax * 8 : 0;
   constexpr int kColsB = (ROWST || ATT) ? 512 * 4 : 0, kStatB = ROWST ? BM * 8 : 0;
-  __shared__ __attribute__((aligned(16))) char smem[kStageB + kRowsB + kColsB + kStatB];
+  constexpr int kAttB = ATTG ? 512 * 4 + 128 : 0;  // key bias [S][LK] (S * LK <= 512) | a 128-B row of zeros
+  __shared__ __attribute__((aligned(16))) char smem[kStageB + kRowsB + kColsB + kStatB + kAttB];
+  static_assert(sizeof(smem) <= 160 * 1024, "LDS");
   f16_t* const lds = reinterpret_cast<f16_t*>(smem);
-  float2* const lds_rows = reinterpret_cast<float2*>(smem + kStageB);
+  float2* const lds_rows = reinterpret_cast<float2*>(smem + (ATTG ? STAGE * 2 : kStageB));
   float* const lds_cols = reinterpret_cast<float*>(smem + kStageB + kRowsB);
   float2* const lds_stat = reinterpret_cast<float2*>(smem + kStageB + kRowsB + kColsB);  // (mean, rstd) per row
+  float* const lds_kbias = reinterpret_cast<float*>(smem + kStageB + kRowsB + kColsB + kStatB);
+  f16_t* const lds_zrow = reinterpret_cast<f16_t*>(smem + kStageB + kRowsB + kColsB + kStatB + 512 * 4);
 
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
@@ -57,6 +68,17 @@
 
   int t = MMF_GLDS_FIRST_TILE;
   if (t >= tiles) return;
+  // ATTG: rows per panel = the whole sequences a 256-row tile holds; the partials through a descriptor
+  // over the buffer's whole 256-row blocks (a panel's 256 rows may end past them: those read as zeros)
+  int att_S = 0, att_rows = BM;
+  if constexpr (ATTG) {
+    att_S = BM / g.att_L;
+    att_rows = att_S * g.att_L;
+    if (tid < 32) reinterpret_cast<uint32_t*>(lds_zrow)[tid] = 0u;  // (visible after the first barrier below)
+  }
+  const rsrc_t rstat = make_rsrc(ATTG ? g.ln_in : nullptr, (uint32_t)((M + BM - 1) / BM * BM) * (uint32_t)g.ln_in_P * 8u);
+  // first row of row panel tm
+  auto row0_of = [&](int tm_) { return ATTG ? tm_ * att_rows : tm_ * BM; };
   GST_INIT()
   int tnext = 0;
   // s_setprio 1 for waves 0-3 (+0.4 % on the step, round-1 A/B; the old option gemm_prio = 2)
@@ -77,8 +99,9 @@
     int tm_, tn_;
     tile_coords(tile, tilesM, tilesN, gm, tm_, tn_);
     f16_t* nb = lds + buf * SOFF;
-    if (bufA && tm_ * BM + BM <= M) glds_tile_buf<BM, NW>(ra, (uint32_t)g.lda * 2u, tm_ * BM, kt * BK, aoff, nb, wave);
-    else glds_tile<BM, NW>(g.A, g.lda, tm_ * BM, M, kt * BK, nb, wave, lane);
+    if (bufA && row0_of(tm_) + BM <= M)
+      glds_tile_buf<BM, NW>(ra, (uint32_t)g.lda * 2u, row0_of(tm_), kt * BK, aoff, nb, wave);
+    else glds_tile<BM, NW>(g.A, g.lda, row0_of(tm_), M, kt * BK, nb, wave, lane);
     if (bufW && tn_ * BN + BN <= N)
       glds_tile_buf<BN, NW>(rw, (uint32_t)g.ldw * 2u, tn_ * BN, kt * BK, woff, nb + BM * BK, wave);
     else glds_tile<BN, NW>(g.W, g.ldw, tn_ * BN, N, kt * BK, nb + BM * BK, wave, lane);
@@ -110,14 +133,19 @@
   // has left the previous tile's epilogue by then; the K-step barriers' vmcnt(0) covers them)
   auto epi_dma = [&](int m0_, int n0_) {
     typedef __attribute__((address_space(3))) char lds_char_t;
-    if constexpr (ROWST) {  // the 256 rows' partials: 256 * P * 8 B, contiguous, whole KBs
+    if constexpr (ATTG) {
+      const uint32_t bytes = (uint32_t)BM * g.ln_in_P * 8u, base = (uint32_t)m0_ * (uint32_t)g.ln_in_P * 8u;
+      for (uint32_t off = (uint32_t)wave * 1024u; off < bytes; off += NW * 1024u)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rstat, (lds_void_t*)((lds_char_t*)lds_rows + off), 16,
+                                                 base + off + (uint32_t)lane * 16u, 0, 0, 0);
+    } else if constexpr (ROWST) {  // the 256 rows' partials: 256 * P * 8 B, contiguous, whole KBs
       const uint32_t bytes = (uint32_t)BM * g.ln_in_P * 8u;
       const char* src = reinterpret_cast<const char*>(g.ln_in) + (size_t)m0_ * g.ln_in_P * 8;
       for (uint32_t off = (uint32_t)wave * 1024u; off < bytes; off += NW * 1024u)
         __builtin_amdgcn_global_load_lds((const void*)(src + off + lane * 16),
                                          (lds_void_t*)((lds_char_t*)lds_rows + off), 16, 0, 0);
     }
-    if constexpr (EPI == 1) {  // u[n0 .. n0 + 256)
+    if constexpr (LNC) {  // u[n0 .. n0 + 256)
       if (wave == NW - 1)
         __builtin_amdgcn_global_load_lds((const void*)(g.ln_u + n0_ + lane * 4), (lds_void_t*)lds_cols, 16, 0, 0);
     }
@@ -135,7 +163,7 @@
     GST()  // tile start (= the previous tile's epilogue end)
     int tm, tn;
     tile_coords(t, tilesM, tilesN, gm, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
+    const int m0 = row0_of(tm), n0 = tn * BN;
     f32x4 acc[NI][MI];
 #pragma unroll
     for (int i = 0; i < NI; ++i)
@@ -165,7 +193,7 @@
             // 256x192 tiles have register room: all kLnPMax partial slots read at once, one LDS
             // latency.  Slots p >= P belong to the next rows or lie past the DMA'd block (any bit
             // pattern, NaN included), so they are SELECTED out, never weighted by 0.
-            const int P = g.ln_in_P, tnin = g.ln_in_tn, C = EPI == 1 ? g.K : N;
+            const int P = g.ln_in_P, tnin = g.ln_in_tn, C = LNC ? g.K : N;
             const float2* pr = lds_rows + tid * P;
             float2 pv[kLnPMax];
             float nv[kLnPMax];
@@ -190,7 +218,7 @@
             }
             lds_stat[tid] = make_float2(mean, rsqrtf(s2 / (float)C + g.ln_eps));
           } else if (tid < BM) {
-            const int P = g.ln_in_P, tnin = g.ln_in_tn, C = EPI == 1 ? g.K : N;
+            const int P = g.ln_in_P, tnin = g.ln_in_tn, C = LNC ? g.K : N;
             const float2* pr = lds_rows + tid * P;
             float s1 = 0.f;
 #pragma unroll 1
@@ -221,7 +249,7 @@
           kt_d = 0;
           if (tnext < tiles) tile_coords(tnext, tilesM, tilesN, gm, tm_d, tn_d);  // (else: reload slab 0 of t)
         }
-        dma_a = (uint32_t)(tm_d * BM) * (uint32_t)g.lda * 2u + (uint32_t)(kt_d * BK) * 2u;
+        dma_a = (uint32_t)row0_of(tm_d) * (uint32_t)g.lda * 2u + (uint32_t)(kt_d * BK) * 2u;
         dma_w = (uint32_t)(tn_d * BN) * (uint32_t)g.ldw * 2u + (uint32_t)(kt_d * BK) * 2u;
       } else if (kt + 1 < nk) {
         stage(cur ^ 1, t, kt + 1);
@@ -347,7 +375,41 @@
     // fetched at tile start and residual rows are loaded one fragment row AHEAD of the stores (one
     // vmcnt counter covers loads and stores in issue order).
     // lazy LN: (mean, rstd) of fragment row j -> lds_stat[wm * TM + j * 16 + fr] (computed at kt = 2)
-    if constexpr (ATT) {
+    if constexpr (ATTG) {
+      // q | k | v of head tn for the tile's 256 rows: r (acc - mean u) + c rounded to fp16 as the EPI 1 store
+      // rounds it, into the 96 KB window (the stage the last K-step freed + the gap) as three [256][64]
+      // images in attention.hip's swizzle; rows past the last whole sequence are written and never read
+      f16_t* const win = lds + ((cur ^ 1) ? SOFF + STAGE - 49152 : 0);
+#pragma unroll
+      for (int j = 0; j < MI; ++j) {
+        const int row = wm * TM + j * 16 + fr;
+        const float2 st = lds_stat[row];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const int c = wn * TN + i * 16 + fg * 4, part = c >> 6, d = c & 63;
+          float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+          const float4 u = *reinterpret_cast<const float4*>(lds_cols + wn * TN + i * 16 + fg * 4);
+          v[0] = st.y * (v[0] - st.x * u.x);
+          v[1] = st.y * (v[1] - st.x * u.y);
+          v[2] = st.y * (v[2] - st.x * u.z);
+          v[3] = st.y * (v[3] - st.x * u.w);
+          const float4 bi = bias_of(i);
+          v[0] += bi.x;
+          v[1] += bi.y;
+          v[2] += bi.z;
+          v[3] += bi.w;
+          *reinterpret_cast<uint2*>(win + part * 16384 + swz(row, d >> 3) + (d & 7)) =
+              make_uint2(pack2h(v[0], v[1]), pack2h(v[2], v[3]));
+        }
+      }
+      switch ((g.att_L + 31) >> 5) {  // keys padded to 32, as launch_attention picks LK
+        case 1: attention_epilogue_seq<32, EPI == 6>(g, win, lds_zrow, lds_kbias, m0, tn, M, att_S, wave, tid); break;
+        case 2: attention_epilogue_seq<64, EPI == 6>(g, win, lds_zrow, lds_kbias, m0, tn, M, att_S, wave, tid); break;
+        case 3: attention_epilogue_seq<96, EPI == 6>(g, win, lds_zrow, lds_kbias, m0, tn, M, att_S, wave, tid); break;
+        default: attention_epilogue_seq<128, EPI == 6>(g, win, lds_zrow, lds_kbias, m0, tn, M, att_S, wave, tid);
+      }
+      continue;
+    } else if constexpr (ATT) {
       attention_epilogue(g, acc, bias_r, lds + ((cur ^ 1) ? SOFF + STAGE - 49152 : 0), lds_cols, m0, tn, M, wm, wn,
                          wave, tid, fr, fg);
       continue;

@@ -67,6 +67,9 @@ struct EncLayer {
   Lin16 qkv_f, fc1_f;
   float *qkv_u = nullptr, *fc1_u = nullptr;
   Lin16 qkv_h;  // RoBERTa: the fused QKV with rows interleaved per head, [q_h; k_h; v_h] (gemm.hip epi 3)
+  // CLIP: qkv_f / qkv_u with the same per-head row interleave (gemm.hip epi 5, option clip_qkv_attn)
+  Lin16 qkv_fh;
+  float* qkv_uh = nullptr;
   // RoBERTa precise mode (text_hilo = 2, precise.hip): [W_hi | W_hi | W_lo] along K (in = 3 K), the
   // bias shared with the fp16 copy
   Lin16 qkv3, o3, fc13, fc23;
@@ -155,6 +158,8 @@ struct Options {
   int dw_cw32 = 1;      // 32-channel groups for the standalone depthwise convs (effnet.hip dw_geometry; B=512 3.648 -> 3.595 ms)
   int effnet_chunks = 2;  // mmf_effnet_forward: batch chunks on concurrent streams (B=512: 3.82 -> 3.57 ms in bench.py)
   int qkv_attn = 1;     // RoBERTa L = 128: attention in the QKV GEMM's epilogue (gemm.hip epi 3)
+  int clip_qkv_attn = 1;  // CLIP towers, lazy LN: attention in the QKV consumer's epilogue (gemm.hip epi 5; bit 1 ViT,
+                        // bit 2 text tower: 0 / 1 = neither / both, 2 = ViT only, 4 = text only)
   int mt_enqueue = 64;  // batches of <= this many pairs: the towers enqueued by host threads side by side
   int last_q1 = 1;      // compact last encoder layers: K / V of every row, Q + attention of the pooled rows only
                         // (bit 1: RoBERTa -- QKV 4.5 -> K/V 3 persistent rounds; bit 2: CLIP towers, whose K/V
@@ -359,7 +364,7 @@ int free_group(mmf_handle* h, int group);
 // ---- per-kernel timing: two hipEvents around each launch while profiling is on ------------
 // GEMM launches are profiled per (tile instantiation, epilogue, activation) -- one kernel symbol
 // each, so the numbers line up with a rocprofv3 kernel trace of the same run.
-constexpr int kGemmActs = 5, kGemmEpis = 5;
+constexpr int kGemmActs = 5, kGemmEpis = 6;
 enum ProfKind {
   PK_GEMM0 = 0, PK_GEMM_LAST = kGemmConfigs * kGemmEpis * kGemmActs - 1, PK_ATTN, PK_LN, PK_EMBED, PK_IM2COL, PK_STEM, PK_DW, PK_SE,
   PK_GAP, PK_HEADS, PK_VAULT, PK_FUSION, PK_PW32, PK_COUNT
@@ -415,9 +420,12 @@ inline int gemm(mmf_handle* h, GemmArgs g, hipStream_t s) {
   const double out_b = (g.c32 ? 4.0 : 0.0) + (g.c16 ? 2.0 : 0.0) + (g.res32 ? 4.0 : 0.0) + (g.res16 ? 2.0 : 0.0);
   // epi 3 also runs the attention of its rows (4 L^2 64 flops per sequence and head, L = 128) and
   // writes ctx (N / 3 columns) instead of qkv
-  const double att = g.epi == 3 ? 4.0 * (M / 128) * (N / 192) * 128.0 * 128.0 * 64.0 : 0.0;
+  // (epi 5: the same for sequences of att_L rows)
+  const double att = g.epi == 3   ? 4.0 * (M / 128) * (N / 192) * 128.0 * 128.0 * 64.0
+                     : g.epi == 5 ? 4.0 * (M / g.att_L) * (N / 192) * (double)g.att_L * g.att_L * 64.0
+                                  : 0.0;
   ProfScope ps(h, s, (gemm_config(g) * kGemmEpis + g.epi) * kGemmActs + g.act, 2.0 * M * N * K + att,
-               2.0 * (M * K + N * K) + M * (g.epi == 3 ? N / 3 : N) * out_b * (g.epi == 4 && g.split_lo ? 3 : 1));
+               2.0 * (M * K + N * K) + M * (g.epi == 3 || g.epi == 5 ? N / 3 : N) * out_b * (g.epi == 4 && g.split_lo ? 3 : 1));
   HIPCHK(launch_gemm(g, s));
   return 0;
 }

@@ -44,6 +44,12 @@ struct GemmArgs {
   // operand row: c16[m * ldc + n] = hi, and with split_lo also [+ N] = lo = fp16(out - hi), [+ 2N] = hi
   // (ldc >= 3N), so the fp32 hidden and its split3 pass are never formed
   int split_lo;
+  // epi 5 (CLIP towers, option clip_qkv_attn): the lazy-LN consumer of epi 1 on a QKV weight whose folded
+  // (W', u, c) rows are interleaved per head as for epi 3, with the attention of the tile's
+  // floor(256 / att_L) whole sequences of att_L rows (16 .. 128) in its epilogue: row panel tm starts at
+  // row tm * floor(256 / att_L) * att_L, ctx [M][ldc] goes to c16 and qkv is never stored.  amask:
+  // int32 [M / att_L][att_L] (1 keep) or null; att_causal: key j of a sequence is visible to queries >= j
+  int att_L, att_causal;
 };
 // whether launch_gemm accepts a (epi != 0) epilogue for these arguments (the host falls back to
 // the plain path otherwise)

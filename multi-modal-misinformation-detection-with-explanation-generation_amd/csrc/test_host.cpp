@@ -276,6 +276,29 @@ int mmf_gemm_f16_attn(const void* A, int lda, const void* W, int ldw, const floa
   return test_launch_rc(launch_gemm(g, (hipStream_t)stream), "gemm (attention epilogue)");
 }
 
+int mmf_gemm_f16_ln_attn(const void* A, int lda, const void* W, int ldw, const float* bias, const void* ln_in, int P,
+                         int tn, const float* ln_u, float eps, const int32_t* amask, int L, int causal, void* ctx,
+                         int ldc, int M, int N, int K, void* stream) {
+  if (!A || !W || !bias || !ln_in || !ln_u || !ctx) return fail(MMF_EINVAL, "null argument");
+  if (M <= 0 || N <= 0 || K <= 0 || L <= 0 || lda < K || ldw < K)
+    return fail(MMF_EINVAL, "gemm: bad shape (M=%d N=%d K=%d L=%d lda=%d ldw=%d)", M, N, K, L, lda, ldw);
+  GemmArgs g = splitk_args(A, lda, W, ldw, bias, nullptr, nullptr, nullptr, ctx, ldc, M, N, K, 0);
+  g.ldr = 0;
+  g.epi = 5;
+  g.ln_in = (const float2*)ln_in;
+  g.ln_in_P = P;
+  g.ln_in_tn = tn;
+  g.ln_u = ln_u;
+  g.ln_eps = eps;
+  g.amask = amask;
+  g.att_L = L;
+  g.att_causal = causal ? 1 : 0;
+  if (!gemm_epi_ok(g))
+    return fail(MMF_EINVAL, "lazy-LN attention epilogue not applicable (M=%d N=%d K=%d L=%d P=%d tn=%d ldc=%d)", M, N, K, L,
+                P, tn, ldc);
+  return test_launch_rc(launch_gemm(g, (hipStream_t)stream), "gemm (lazy-LN consumer + attention epilogue)");
+}
+
 int mmf_gemm_ln_tn(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return fail(MMF_EINVAL, "gemm_ln_tn: bad shape");
   GemmArgs g = splitk_args(nullptr, K, nullptr, K, nullptr, nullptr, nullptr, nullptr, nullptr, N, M, N, K, 0);

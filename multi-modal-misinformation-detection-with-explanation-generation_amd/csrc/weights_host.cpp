@@ -112,8 +112,10 @@ int load_lin(mmf_handle* h, Lin16* l, const std::string& p, int out, int in, boo
 // LN(x) W^T + b with LN = (gamma, beta) folded (gemm.hip lazy LN): w' = fp16(w diag(gamma)),
 // u = sum_k w'[n][k] over the fp16 values (so acc - mean u is exactly sum_k w'(s_k - mean)),
 // c = b + w beta, both in double
+// dst_h / u_h (nullable; a fused QKV, out = 3 in): the same (w', u, c) with rows interleaved per head as qkv_h
 int fold_ln_lin(mmf_handle* h, Lin16* dst, float** u, const std::vector<float>& w, const std::vector<float>& b,
-                int out, int in, const std::vector<float>& g, const std::vector<float>& beta) {
+                int out, int in, const std::vector<float>& g, const std::vector<float>& beta, Lin16* dst_h = nullptr,
+                float** u_h = nullptr) {
   std::vector<float> wf((size_t)out * in), uv(out), c(out);
   for (int n = 0; n < out; ++n) {
     double su = 0.0, sc = b[n];
@@ -131,6 +133,23 @@ int fold_ln_lin(mmf_handle* h, Lin16* dst, float** u, const std::vector<float>& 
   CHK(up_f32_padded(h, u, uv));
   dst->out = out;
   dst->in = in;
+  if (dst_h) {
+    const int H = in;
+    std::vector<float> wh(wf.size()), uh(out), ch(out);
+    for (int hd = 0; hd < H / 64; ++hd)
+      for (int part = 0; part < 3; ++part)
+        for (int d = 0; d < 64; ++d) {
+          const size_t src = (size_t)part * H + hd * 64 + d, dr = (size_t)hd * 192 + part * 64 + d;
+          std::memcpy(wh.data() + dr * in, wf.data() + src * in, sizeof(float) * in);
+          uh[dr] = uv[src];
+          ch[dr] = c[src];
+        }
+    CHK(up_f16(h, &dst_h->w, wh));
+    CHK(up_f32_padded(h, &dst_h->b, ch));
+    CHK(up_f32_padded(h, u_h, uh));
+    dst_h->out = out;
+    dst_h->in = in;
+  }
   return 0;
 }
 int fold_ln_named(mmf_handle* h, Lin16* dst, float** u, const std::string& lin, int out, int in,
@@ -176,7 +195,7 @@ int load_qkv(mmf_handle* h, EncLayer* L, const std::string& q, const std::string
   if (ln.empty()) return 0;
   GET(g, ln + ".weight", H);
   GET(be, ln + ".bias", H);
-  return fold_ln_lin(h, &L->qkv_f, &L->qkv_u, w, b, 3 * H, H, g->f, be->f);
+  return fold_ln_lin(h, &L->qkv_f, &L->qkv_u, w, b, 3 * H, H, g->f, be->f, &L->qkv_fh, &L->qkv_uh);
 }
 
 // BatchNorm (eval) folded into the preceding conv: w' = w * g/sqrt(v+eps), b' = beta - m*g/sqrt(v+eps)

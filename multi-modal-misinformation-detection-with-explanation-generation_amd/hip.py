@@ -114,6 +114,7 @@ SIGNATURES = {
     "mmf_gemm_f16_ln_producer": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mmf_gemm_f16_ln_consumer": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "mmf_gemm_f16_attn": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "mmf_gemm_f16_ln_attn": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _F, _P, _I, _I, _P, _I, _I, _I, _I, _P]),
     # the closing fp32 kernels and the vault's stages on raw operands (csrc/test_host.cpp)
     "mmf_text_heads_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     "mmf_text_cls_rows_f32": (_I, [_P, _I, _P, _P, _I, _P]),

@@ -20,7 +20,7 @@ from .hip import check
 PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
 PEAK_BF16_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
-NK = 512  # >= the library's PK_COUNT (kGemmConfigs x 5 epilogues x 5 activations + 12 other kinds)
+NK = 640  # >= the library's PK_COUNT (kGemmConfigs x 6 epilogues x 5 activations + 12 other kinds)
 
 
 def profile_kernels(eng, step: Callable[[], None], steps: int) -> List[Dict]:
@@ -60,6 +60,7 @@ def kind_symbol(kind: str) -> str:
         return kind
     dims = m.group(2).split(",")
     epi = m.group(4) or "0"
+    # (epi 5, the CLIP QKV consumer with the attention epilogue, is EPI 5 for the ViT and 6 for the causal text tower)
     # (then the measurement-build selector DBG, 0 in production)
     if m.group(1) == "glds":
         return f"gemm_glds_kernel<{', '.join(dims + [m.group(3), 'false', epi, '0'])}>"
