@@ -135,6 +135,55 @@ int mmf_effnet_forward(mmf_handle* h, const uint8_t* img, int B, float* logits, 
 int mmf_effnet_forward_f32(mmf_handle* h, const float* x, int B, float* logits, float* deepfake_score,
                            void* stream);
 
+/* The frozen part of the deepfake-classifier training (train_cifake_forensics.py runs the whole backbone for
+ * every minibatch of every epoch): the row the deployed classifier reads, the global average over the 7x7
+ * head output (misinfo_forensics.py:72-76).  img as mmf_effnet_forward; pooled fp32 [B, 1280], 16-byte
+ * aligned.  The launch sequence of mmf_effnet_forward for the tower in use (fp16, or fp32 under option
+ * effnet_fp32) on one stream, without the classifier: per channel the pixels summed in ascending order in
+ * fp32, times 1 / 49, as the classifier kernels form it.  An overflowed fp16 activation gives a non-finite
+ * row, as it gives a non-finite score there. */
+int mmf_effnet_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, void* stream);
+
+/* RandomHorizontalFlip's mirror on a staged uint8 window (train_cifake_forensics.py:39-45: Resize, then the
+ * flip): dst[b][y][x][c] = src[b][y][W-1-x][c].  No handle.  dst and src must not overlap.  MMF_EINVAL with
+ * nothing launched: a NULL pointer, a non-positive dimension, dst == src. */
+int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, void* stream);
+
+/* Training of the deployed deepfake classifier -- Dropout(0.2) then Linear(1280, 2) on the pooled row
+ * (misinfo_forensics.py:72-76) -- on cached pooled rows (train_cifake_forensics.py:187-216 the loop body, stated
+ * for a frozen backbone): ONE epoch in ONE launch by one workgroup.  For each of the ceil(N / batch)
+ * minibatches: xd = x * keep * scale, scale = fp32 of 1 / (1 - p_drop) computed in double; logits = xd W^T + b;
+ * mean cross-entropy; backward to both tensors; torch.optim.Adam (:334-337): weight_decay * p added to the
+ * gradient (0 leaves it bit-unchanged), bias correction by step0 + s + 1, constant lr, no clipping.  No
+ * handle; asynchronous on `stream`.  All fp32, the step scalars computed in double from the step number
+ * alone; every reduction has a fixed order that depends on the minibatch's row count alone
+ * (csrc/effnet_train.hip), so results are bit-reproducible and do not depend on how an epoch is split into
+ * launches.
+ *   feat fp32 [R][1280], labels int32 [R] (read as label & 1): a BANK of R rows; perm int32 [N]: the epoch's
+ *     N entries, each a bank row (an entry outside [0, R) is clamped, so no input makes the kernel read out
+ *     of bounds).  Minibatch s takes positions s*batch .. of perm; the last may be short (its mean is over
+ *     its own rows).  R and N are separate so that a caller can offer a second view of every image (the
+ *     mirrored one) as further bank rows.
+ *   keep uint64 [N][20] or NULL: keep[i] is the dropout mask of the row at POSITION i of the epoch order,
+ *     word w bit j set = input channel 64 w + j kept and scaled; NULL = no dropout, no scaling.
+ *   params, exp_avg, exp_avg_sq fp32 [MMF_EFFCLS_PARAMS], state-dict order, updated in place.
+ *   step_loss fp32 [nsteps]: the minibatch's mean loss (train-mode logits, before its update); step_correct
+ *     int32 [nsteps]: rows with argmax(logits) == label (a tie is class 0, as torch.max); grad_out fp32
+ *     [MMF_EFFCLS_PARAMS] or NULL: the last minibatch's loss gradient (what p.grad holds: without the decay).
+ * Buffers are 4-byte aligned, keep 8-byte.  MMF_EINVAL with nothing launched: a NULL required pointer, R < 1,
+ * N < 1, batch outside 1..64, step0 < 0, p_drop outside [0, 1), a misaligned buffer. */
+#define MMF_EFFCLS_PARAMS 2562  /* classifier.1.weight [2][1280], classifier.1.bias [2] */
+int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, const int32_t* perm, int N,
+                           const uint64_t* keep, float p_drop, int batch, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, int step0, float* params, float* exp_avg,
+                           float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* grad_out, void* stream);
+
+/* validate (train_cifake_forensics.py:236-276) on cached pooled rows: forward only, no dropout, consecutive
+ * batches of the R bank rows in file order, one workgroup per batch.  batch_loss fp32 [ceil(R / batch)]: each
+ * batch's mean cross-entropy; row_logits fp32 [R][2].  Errors as the training call's. */
+int mmf_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, const float* params,
+                    float* batch_loss, float* row_logits, void* stream);
+
 /* CLIP image embedding — get_image_features + L2 normalisation (misinfo_forensics.py:395-401,
  * 432-439).  img uint8 [B, 224, 224, 3] (CLIP-preprocessed geometry); emb fp32 [B, 512] unit. */
 int mmf_clip_image(mmf_handle* h, const uint8_t* img, int B, float* emb_unit, void* stream);

@@ -1,0 +1,326 @@
+"""The EfficientNet deepfake classifier trained on the device (train_cifake_forensics.py:71-379).
+
+The script fine-tunes a timm EfficientNet inside another model class and saves a timm-named state dict (:374) that
+the inference constructor's fallback path applies to nothing.  Here the DEPLOYED classifier --
+Dropout(0.2) then Linear(1280, 2) on the pooled row (misinfo_forensics.py:72-76) -- is trained on a frozen backbone,
+and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads:
+
+* ``load_cifake_data``: the script's directory contract, balanced sample and 80 / 20 split.
+* ``extract_image_features``: the pooled 1280-wide row of every image, once, through the HIP tower
+  (``Engine.effnet_pooled``) -- and, for the training transform's RandomHorizontalFlip, the row of the mirrored
+  window (``mmf_hflip_u8`` on the staged window, after the Pillow-exact resize: Resize, then the flip, :39-45).
+* ``plan``: per epoch the permutation, the flip draws and the dropout masks.
+* ``ClassifierTrainer``: one ``mmf_effcls_train_epoch`` and one ``mmf_effcls_eval`` call per epoch on the cached
+  rows, a raw state dict on a strictly higher validation accuracy (:372-374), the best classifier put back into
+  the detector.
+* ``train_cifake`` / ``python -m mmf_amd.cifake_training``: the script's entry point.
+
+Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a frozen backbone, where the script
+fine-tunes the whole backbone together with a 1538-d fusion head of another model class.  Further: the deployed
+ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; no ColorJitter, and the flip
+comes from two cached views; fp32, no autocast / GradScaler; a seeded generator instead of the global RNG; file names
+sorted before the seeded shuffle (os.listdir order is arbitrary); unreadable images dropped instead of fed as a blank
+tensor.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import io_utils
+
+BETAS, EPS, WEIGHT_DECAY = (0.9, 0.999), 1e-8, 0.0  # torch.optim.Adam defaults (train_cifake_forensics.py:334-337)
+P_DROP = 0.2                                        # the classifier's Dropout (misinfo_forensics.py:73)
+WIDTH = 1280
+WORDS = WIDTH // 64
+PARAM_KEYS = ("classifier.1.weight", "classifier.1.bias")
+N_PARAMS = 2 * WIDTH + 2  # MMF_EFFCLS_PARAMS
+EXTENSIONS = (".jpg", ".jpeg", ".png")
+DEFAULT_FILE = "efficientnet_cifake_best.pth"
+
+
+# ---------------------------------------------------------------------------------------------
+# the data set
+# ---------------------------------------------------------------------------------------------
+def _images_in(folder: str) -> List[str]:
+    if not os.path.isdir(folder):
+        return []
+    out = []
+    for name in sorted(os.listdir(folder)):
+        path = os.path.join(folder, name)
+        if os.path.isfile(path) and name.lower().endswith(EXTENSIONS):
+            out.append(path)
+    return out
+
+
+def load_cifake_data(cifake_root: str, sample_per_label: int = 2500, seed: int = 42):
+    """(train_paths, train_labels, val_paths, val_labels) of a CIFAKE tree (train_cifake_forensics.py:71-151):
+    REAL images from test/REAL, FAKE images from train/FAKE and test/FAKE (.jpg / .jpeg / .png, any case); a
+    balanced sample of min(sample_per_label, n_real, n_fake) per label, 0 = REAL and 1 = FAKE; shuffled by
+    ``random.Random(seed)`` and split 80 / 20.  ValueError when either label has no image.  File names are sorted
+    before the shuffles, so the result is a function of the tree and the seed alone."""
+    real = _images_in(os.path.join(cifake_root, "test", "REAL"))
+    fake = _images_in(os.path.join(cifake_root, "train", "FAKE")) + _images_in(os.path.join(cifake_root, "test", "FAKE"))
+    if not real or not fake:
+        raise ValueError(f"Insufficient data! REAL: {len(real)}, FAKE: {len(fake)}")
+    rng = random.Random(seed)
+    rng.shuffle(real)
+    rng.shuffle(fake)
+    n = min(int(sample_per_label), len(real), len(fake))
+    rows = [(p, 0) for p in real[:n]] + [(p, 1) for p in fake[:n]]
+    rng.shuffle(rows)
+    cut = int(0.8 * len(rows))
+    paths, labels = [p for p, _ in rows], [y for _, y in rows]
+    return paths[:cut], labels[:cut], paths[cut:], labels[cut:]
+
+
+# ---------------------------------------------------------------------------------------------
+# cached features
+# ---------------------------------------------------------------------------------------------
+def _black():
+    return io_utils.Image.new("RGB", (224, 224), (0, 0, 0))
+
+
+def extract_image_features(forensics, image_paths: Sequence, flip: bool = False):
+    """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
+    the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
+    staged as analyze_pairs stages them (device JPEG decode where it applies, Pillow otherwise, the Pillow-exact
+    squash to 224 x 224 on the device), the window mirrored on the device, both through ``Engine.effnet_pooled``.
+    An image that cannot be read gives ok False and zero rows."""
+    paths = list(image_paths)
+    N = len(paths)
+    feats = np.zeros((N, WIDTH), np.float32)
+    flipped = np.zeros((N, WIDTH), np.float32) if flip else None
+    ok = np.ones(N, bool)
+    cap = forensics.engine.max_batch
+    chunks = [(a, min(a + cap, N)) for a in range(0, N, cap)]
+    if chunks:
+        forensics._ensure_jpeg_stager()
+        forensics.detector.sync(("effnet",))
+
+    def host_stage(a, b):
+        try:
+            return a, b, forensics._stage_images(paths[a:b])
+        except Exception:  # noqa: BLE001  (a file of the chunk does not open: each on its own, marked where it fails)
+            pils = []
+            for i, p in enumerate(paths[a:b]):
+                try:
+                    pils.append(io_utils.to_pil(p))
+                except Exception:  # noqa: BLE001
+                    pils.append(_black())
+                    ok[a + i] = False
+            return a, b, forensics._stage_images(pils)
+
+    def device_part(staged):
+        a, b, rgb = staged
+        eff, _ = forensics._windows(*rgb)
+        feats[a:b] = forensics.engine.effnet_pooled(eff).cpu().numpy()
+        if flip:
+            flipped[a:b] = forensics.engine.effnet_pooled(forensics.engine.hflip(eff)).cpu().numpy()
+
+    if chunks:
+        forensics._run_chunks(chunks, host_stage, device_part)
+    feats[~ok] = 0
+    if flip:
+        flipped[~ok] = 0
+        return feats, flipped, ok
+    return feats, ok
+
+
+# ---------------------------------------------------------------------------------------------
+# the epoch plan
+# ---------------------------------------------------------------------------------------------
+def pack_keep(mask: np.ndarray) -> np.ndarray:
+    """bool [N, 1280] -> uint64 [N, 20]: word w bit j = input channel 64 w + j kept."""
+    m = np.asarray(mask, dtype=bool).reshape(-1, WORDS, 64).astype(np.uint64)
+    return (m << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
+
+
+def unpack_keep(keep: np.ndarray) -> np.ndarray:
+    """uint64 [N, 20] -> bool [N, 1280]."""
+    k = np.asarray(keep, np.uint64).reshape(-1, WORDS, 1)
+    return ((k >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(-1, WIDTH)
+
+
+def plan(N: int, batch_size: int, epochs: int, seed: int, flip: bool = True):
+    """Per epoch (perm int32 [N], keep uint64 [N, 20], flipped bool [N]) from one
+    ``torch.Generator().manual_seed(seed)``: the DataLoader's shuffle as ``torch.randperm(N)``; with ``flip`` the
+    RandomHorizontalFlip draws ``torch.rand(N) < 0.5`` indexed by data-set row (all False without); the dropout
+    masks ``torch.rand(N, 1280) >= 0.2`` (row i = the row at position i of the epoch order).  ``perm`` holds the
+    KERNEL's entries: row + N where the row is flipped, the mirrored view being rows N .. 2N - 1 of the bank."""
+    g = torch.Generator().manual_seed(int(seed))
+    out = []
+    for _ in range(int(epochs)):
+        order = torch.randperm(N, generator=g).numpy().astype(np.int64)
+        flipped = (torch.rand(N, generator=g) < 0.5).numpy() if flip else np.zeros(N, bool)
+        keep = pack_keep((torch.rand(N, WIDTH, generator=g) >= P_DROP).numpy())
+        out.append(((order + N * flipped[order]).astype(np.int32), keep, flipped))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the trainer
+# ---------------------------------------------------------------------------------------------
+def _classifier(detector):
+    return getattr(detector.efficientnet.classifier, "1")
+
+
+def flatten_classifier(detector) -> torch.Tensor:
+    """classifier.1.weight | classifier.1.bias of the detector's EfficientNet as one float32 [2562] tensor."""
+    lin = _classifier(detector)
+    flat = torch.cat([lin.weight.detach().reshape(-1).float(), lin.bias.detach().reshape(-1).float()])
+    if flat.numel() != N_PARAMS:
+        raise ValueError(f"a classifier of {flat.numel()} parameters, expected {N_PARAMS}")
+    return flat
+
+
+class ClassifierTrainer:
+    """The training loop of train_cifake_forensics.py:351-376 on cached pooled rows: per epoch one training call and
+    one validation call on the device.  ``fit`` ends with ONE re-pack of the detector's effnet component
+    (``detector.sync``), which also re-runs the load-time precision calibration on the new classifier."""
+
+    def __init__(self, forensics, batch_size: int = 16, epochs: int = 10, lr: float = 1e-4, seed: int = 0,
+                 flip: bool = True, weight_decay: float = WEIGHT_DECAY):
+        if not 1 <= int(batch_size) <= 64:
+            raise ValueError(f"batch_size must be in 1..64, got {batch_size}")
+        self.forensics, self.batch_size, self.epochs = forensics, int(batch_size), int(epochs)
+        self.lr, self.seed, self.flip, self.weight_decay = float(lr), int(seed), bool(flip), float(weight_decay)
+
+    @staticmethod
+    def _data(feats, labels, what):
+        x = np.ascontiguousarray(np.asarray(feats, dtype=np.float32))
+        y = np.asarray(labels)
+        if x.ndim != 2 or x.shape[1] != WIDTH or len(x) == 0 or y.shape != (x.shape[0],):
+            raise ValueError(f"{what} features {x.shape} / labels {y.shape} must be [N, 1280] / [N], N >= 1")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{what} features must be finite")
+        if not np.isin(y, (0, 1)).all():
+            raise ValueError(f"{what} labels must be 0 or 1")
+        return x, y.astype(np.int32)
+
+    def fit(self, train, train_labels, val, val_labels, checkpoint_path: Optional[str] = None,
+            save_full_model: bool = False) -> List[dict]:
+        """``train``: float32 [N, 1280], or with ``flip`` the pair (rows, rows of the mirrored windows)."""
+        f = self.forensics
+        eng, det = f.engine, f.detector
+        dev = eng.device
+        if self.flip:
+            if not (isinstance(train, (tuple, list)) and len(train) == 2):
+                raise ValueError("flip=True needs train = (features, features of the mirrored windows)")
+            xt, yt = self._data(train[0], train_labels, "training")
+            xf, _ = self._data(train[1], train_labels, "mirrored training")
+            bank, bank_labels = np.concatenate([xt, xf]), np.concatenate([yt, yt])
+        else:
+            bank, bank_labels = self._data(train, train_labels, "training")
+            yt = bank_labels
+        xv, yv = self._data(val, val_labels, "validation")
+        N, bs = len(yt), self.batch_size
+        bank, bank_labels, xv, yv_d = (torch.from_numpy(a).to(dev) for a in (bank, bank_labels, xv, yv))
+        params = flatten_classifier(det).to(dev).contiguous()
+        m, v = torch.zeros_like(params), torch.zeros_like(params)
+        spe = -(-N // bs)
+        history, best_acc, best, step0 = [], 0.0, None, 0
+        for epoch, (perm, keep, _) in enumerate(plan(N, bs, self.epochs, self.seed, self.flip), 1):
+            sl, sc = eng.effcls_train_epoch(bank, bank_labels, torch.from_numpy(perm).to(dev),
+                                            torch.from_numpy(keep.view(np.int64)).to(dev), P_DROP, bs, self.lr, BETAS,
+                                            EPS, self.weight_decay, step0, params, m, v)
+            bl, lg = eng.effcls_eval(xv, yv_d, bs, params)
+            step0 += spe
+            train_loss = float(sl.cpu().numpy().astype(np.float64).mean())  # running_loss / len(dataloader) (:224)
+            train_acc = float(100 * int(sc.cpu().numpy().astype(np.int64).sum()) / N)
+            val_loss = float(bl.cpu().numpy().astype(np.float64).mean())    # :270
+            if not (np.isfinite(train_loss) and np.isfinite(val_loss)):
+                raise FloatingPointError(f"epoch {epoch}: the loss is not finite")
+            lg = lg.cpu().numpy()
+            pred = (lg[:, 1] > lg[:, 0]).astype(np.int64)  # torch.max: a tie is class 0
+            val_acc = float(100 * int((pred == yv).sum()) / len(yv))
+            history.append({"epoch": epoch, "train_loss": train_loss, "train_acc": train_acc, "val_loss": val_loss,
+                            "val_acc": val_acc})
+            if val_acc > best_acc:  # :372
+                best_acc, best = val_acc, params.clone()
+                if checkpoint_path:
+                    torch.save(self._state(best, save_full_model), checkpoint_path)
+        self.best_val_acc = best_acc
+        self._install(best if best is not None else params)
+        return history
+
+    def _tensors(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        flat = flat.detach().cpu()
+        return {PARAM_KEYS[0]: flat[:2 * WIDTH].reshape(2, WIDTH).clone(), PARAM_KEYS[1]: flat[2 * WIDTH:].clone()}
+
+    def _state(self, flat: torch.Tensor, full: bool) -> Dict[str, torch.Tensor]:
+        """A raw state dict in torchvision names, as the script saves a raw one (:374): the two classifier tensors,
+        or (``full``) the whole detector.efficientnet.state_dict() with them."""
+        cls = self._tensors(flat)
+        if not full:
+            return cls
+        sd = {k: t.detach().cpu() for k, t in self.forensics.detector.efficientnet.state_dict().items()}
+        sd.update(cls)
+        return sd
+
+    def _install(self, flat: torch.Tensor) -> None:
+        """In-place copies bump the parameters' version counters; detector.sync() then re-packs the effnet component
+        and re-runs check_effnet_precision, whose calibration depends on the classifier's logits."""
+        det = self.forensics.detector
+        lin, t = _classifier(det), self._tensors(flat)
+        with torch.no_grad():
+            lin.weight.copy_(t[PARAM_KEYS[0]])
+            lin.bias.copy_(t[PARAM_KEYS[1]])
+        det.sync(("effnet",))
+
+
+# ---------------------------------------------------------------------------------------------
+# the script's entry point
+# ---------------------------------------------------------------------------------------------
+def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epochs: int = 10,
+                 sample_per_label: int = 2500, forensics=None, checkpoint_path: Optional[str] = DEFAULT_FILE, *,
+                 device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False):
+    """train_cifake_forensics.py:276-379: the CIFAKE tree's balanced sample and split, one feature extraction per
+    split (two views of the training images with ``flip``), unreadable images dropped and counted, then the trainer.
+    Returns the history."""
+    tr_p, tr_y, va_p, va_y = load_cifake_data(cifake_root, sample_per_label)
+    print(f"Loaded {len(tr_p)} training samples ({tr_y.count(0)} REAL, {tr_y.count(1)} FAKE)")
+    print(f"Loaded {len(va_p)} validation samples ({va_y.count(0)} REAL, {va_y.count(1)} FAKE)")
+    if forensics is None:
+        from .api import MisinfoForensics
+        forensics = MisinfoForensics(device=device)
+    out = extract_image_features(forensics, tr_p, flip=flip)
+    ok_t = out[-1]
+    xv, ok_v = extract_image_features(forensics, va_p)
+    dropped = int((~ok_t).sum() + (~ok_v).sum())
+    if dropped:
+        print(f"Dropped {dropped} unreadable images")
+    tr_y, va_y = np.asarray(tr_y)[ok_t], np.asarray(va_y)[ok_v]
+    train = (out[0][ok_t], out[1][ok_t]) if flip else out[0][ok_t]
+    trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip)
+    history = trainer.fit(train, tr_y, xv[ok_v], va_y, checkpoint_path=checkpoint_path,
+                          save_full_model=save_full_model)
+    for h in history:
+        print(f"Epoch {h['epoch']}/{epochs}  Train Loss: {h['train_loss']:.4f}, Train Acc: {h['train_acc']:.2f}%  "
+              f"Val Loss: {h['val_loss']:.4f}, Val Acc: {h['val_acc']:.2f}%")
+    print(f"Best validation accuracy: {trainer.best_val_acc:.2f}%")
+    return history
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(prog="python -m mmf_amd.cifake_training",
+                                 description="Train the EfficientNet deepfake classifier on cached pooled rows")
+    ap.add_argument("--root", required=True, help="CIFAKE root (test/REAL, train/FAKE, test/FAKE)")
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--samples-per-label", type=int, default=2500)
+    ap.add_argument("--no-flip", action="store_true", help="train on the unmirrored view alone")
+    ap.add_argument("--checkpoint", default=DEFAULT_FILE)
+    a = ap.parse_args(argv)
+    train_cifake(a.root, batch_size=a.batch_size, lr=a.lr, epochs=a.epochs, sample_per_label=a.samples_per_label,
+                 checkpoint_path=a.checkpoint, flip=not a.no_flip)
+
+
+if __name__ == "__main__":
+    main()

@@ -758,6 +758,53 @@ int mmf_head_eval(const float* feat, const int32_t* labels, int N, int batch, co
   return 0;
 }
 
+int mmf_effnet_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, void* stream) {
+  if (!h || !img || !pooled) return fail(MMF_EINVAL, "null argument");
+  if (!(h->ready & RDY_EFFNET)) return fail(MMF_EINVAL, "EfficientNet not loaded");
+  if ((uintptr_t)pooled & 15) return fail(MMF_EINVAL, "effnet_pooled: pooled must be 16-byte aligned");
+  CHK(check_cap(h, B, 1, 1));
+  HIPCHK(hipSetDevice(h->device));
+  return run_effnet(h, img, nullptr, B, nullptr, nullptr, 1, (hipStream_t)stream, 0, pooled);
+}
+
+int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, void* stream) {
+  if (!src || !dst) return fail(MMF_EINVAL, "null argument");
+  if (B < 1 || H < 1 || W < 1 || C < 1 || (double)B * H * W >= 549755813888.0 /* 2^39 pixels: the grid */)
+    return fail(MMF_EINVAL, "hflip_u8: bad shape (B=%d H=%d W=%d C=%d)", B, H, W, C);
+  if (dst == src) return fail(MMF_EINVAL, "hflip_u8: dst must not be src");
+  HIPCHK(launch_hflip_u8(src, dst, B, H, W, C, (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, const int32_t* perm, int N,
+                           const uint64_t* keep, float p_drop, int batch, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, int step0, float* params, float* exp_avg,
+                           float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* grad_out, void* stream) {
+  if (!feat || !labels || !perm || !params || !exp_avg || !exp_avg_sq || !step_loss || !step_correct)
+    return fail(MMF_EINVAL, "null argument");
+  if (R < 1 || N < 1 || batch < 1 || batch > 64 || step0 < 0 || !(p_drop >= 0.f && p_drop < 1.f))
+    return fail(MMF_EINVAL, "effcls_train_epoch: R=%d N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0) p_drop=%g ([0, 1))",
+                R, N, batch, step0, (double)p_drop);
+  if (((uintptr_t)feat | (uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)step_loss |
+       (uintptr_t)grad_out | (uintptr_t)labels | (uintptr_t)perm | (uintptr_t)step_correct) & 3 ||
+      ((uintptr_t)keep & 7))
+    return fail(MMF_EINVAL, "effcls_train_epoch: pointers must be 4-byte aligned (keep: 8)");
+  HIPCHK(launch_effcls_train_epoch(feat, labels, R, perm, N, keep, p_drop, batch, lr, beta1, beta2, eps, weight_decay,
+                                   step0, params, exp_avg, exp_avg_sq, step_loss, step_correct, grad_out,
+                                   (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, const float* params, float* batch_loss,
+                    float* row_logits, void* stream) {
+  if (!feat || !labels || !params || !batch_loss || !row_logits) return fail(MMF_EINVAL, "null argument");
+  if (R < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "effcls_eval: R=%d (>= 1) batch=%d (1..64)", R, batch);
+  if (((uintptr_t)feat | (uintptr_t)labels | (uintptr_t)params | (uintptr_t)batch_loss | (uintptr_t)row_logits) & 3)
+    return fail(MMF_EINVAL, "effcls_eval: pointers must be 4-byte aligned");
+  HIPCHK(launch_effcls_eval(feat, labels, R, batch, params, batch_loss, row_logits, (hipStream_t)stream));
+  return 0;
+}
+
 int mmf_set_vault(mmf_handle* h, const float* V, int N, int D) {
   if (!h || !V || N <= 0 || D != 512) return fail(MMF_EINVAL, "mmf_set_vault: need N > 0 rows of D = 512");
   HIPCHK(hipSetDevice(h->device));

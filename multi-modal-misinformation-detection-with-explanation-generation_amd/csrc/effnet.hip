@@ -879,6 +879,25 @@ __global__ __launch_bounds__(256) void gap_classifier_kernel(const f16_t* x, int
   }
 }
 
+// The row gap_classifier_kernel's classifier reads (mmf_effnet_pooled): pooled[b][c] = s * inv with s the
+// same ascending-pixel fp32 sum of the fp16 head output; one thread per 8 channels, no classifier.
+__global__ __launch_bounds__(256) void gap_pooled_kernel(const f16_t* x, int HW, int C, float* pooled) {
+  const int bi = blockIdx.x, tid = threadIdx.x;
+  const float inv = 1.0f / (float)HW;
+  for (int c8 = tid * 8; c8 < C; c8 += 256 * 8) {
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const f16_t* xp = x + (size_t)bi * HW * C + c8;
+    for (int p = 0; p < HW; ++p) {
+      const uint4 v = *reinterpret_cast<const uint4*>(xp + (size_t)p * C);
+      s[0] += lo_h(v.x); s[1] += hi_h(v.x); s[2] += lo_h(v.y); s[3] += hi_h(v.y);
+      s[4] += lo_h(v.z); s[5] += hi_h(v.z); s[6] += lo_h(v.w); s[7] += hi_h(v.w);
+    }
+    float* o = pooled + (size_t)bi * C + c8;
+    *reinterpret_cast<float4*>(o) = make_float4(s[0] * inv, s[1] * inv, s[2] * inv, s[3] * inv);
+    *reinterpret_cast<float4*>(o + 4) = make_float4(s[4] * inv, s[5] * inv, s[6] * inv, s[7] * inv);
+  }
+}
+
 }  // namespace
 
 #ifdef MMF_EFF_STAMP
@@ -1107,5 +1126,11 @@ hipError_t launch_gap_classifier(const f16_t* x, int HW, int C, const float* w, 
                                  float* score, int score_stride, int B, hipStream_t s) {
   if (C % 8) return hipErrorInvalidValue;  // 16-B channel groups
   hipLaunchKernelGGL(gap_classifier_kernel, dim3(B), dim3(256), 0, s, x, HW, C, w, b, logits, score, score_stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_gap_pooled(const f16_t* x, int HW, int C, float* pooled, int B, hipStream_t s) {
+  if (C % 8) return hipErrorInvalidValue;  // 16-B channel groups
+  hipLaunchKernelGGL(gap_pooled_kernel, dim3(B), dim3(256), 0, s, x, HW, C, pooled);
   return hipGetLastError();
 }

@@ -444,6 +444,18 @@ __global__ __launch_bounds__(256) void gap32_kernel(const float* __restrict__ x,
   }
 }
 
+// The row gap32_kernel's classifier reads (mmf_effnet_pooled on the fp32 tower): pooled[b][c] = s * inv, the
+// same ascending-pixel sum, no classifier.
+__global__ __launch_bounds__(256) void gap32_pooled_kernel(const float* __restrict__ x, int HW, int C,
+                                                           float* __restrict__ pooled) {
+  const int bi = blockIdx.x;
+  const float inv = 1.0f / (float)HW;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float s = 0.f;
+    for (int p = 0; p < HW; ++p) s += x[((size_t)bi * HW + p) * C + c];
+    pooled[(size_t)bi * C + c] = s * inv;
+  }
+}
 
 }  // namespace
 
@@ -549,3 +561,7 @@ hipError_t launch_gap32(const float* x, int HW, int C, const float* w, const flo
   return hipGetLastError();
 }
 
+hipError_t launch_gap32_pooled(const float* x, int HW, int C, float* pooled, int B, hipStream_t s) {
+  hipLaunchKernelGGL(gap32_pooled_kernel, dim3(B), dim3(256), 0, s, x, HW, C, pooled);
+  return hipGetLastError();
+}

@@ -54,7 +54,7 @@ EffWs<T> eff_ws(const Workspace& w, T* a, T* b, T* exp, T* dw, int b0) {
 // The fp32 tower (option effnet_fp32): same network, same folded weights (fp32 copies of the 1x1
 // convs), activations fp32 throughout -- no fusion, one launch per layer.
 int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score,
-                 int score_stride, hipStream_t s, int img0) {
+                 int score_stride, hipStream_t s, int img0, float* pooled) {
   if (h->ws.e32_cap_b < img0 + B) return fail(MMF_EINVAL, "effnet_fp32: fp32 tower workspaces not reserved");
   const EffWs<float> w = eff_ws(h->ws, h->ws.e32_a, h->ws.e32_b, h->ws.e32_exp, h->ws.e32_dw, img0);
   float* cur = w.e_a;
@@ -101,15 +101,16 @@ int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, fl
                        h->opt.pw32_mfma));
   }
   ProfScope ps(h, s, PK_GAP, (double)B * H * W * 1280 + 4.0 * B * 1280, (double)B * H * W * 1280 * 4);
-  HIPCHK(launch_gap32(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
+  if (pooled) HIPCHK(launch_gap32_pooled(w.e_exp, H * W, 1280, pooled, B, s));
+  else HIPCHK(launch_gap32(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
   return 0;
 }
 
 }  // namespace
 
 int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score, int score_stride,
-               hipStream_t s, int img0) {
-  if (h->opt.effnet_fp32) return run_effnet32(h, img, xf32, B, logits, score, score_stride, s, img0);
+               hipStream_t s, int img0, float* pooled) {
+  if (h->opt.effnet_fp32) return run_effnet32(h, img, xf32, B, logits, score, score_stride, s, img0, pooled);
   const EffWs<f16_t> w = eff_ws(h->ws, h->ws.e_a, h->ws.e_b, h->ws.e_exp, h->ws.e_dw, img0);
   f16_t* cur = w.e_a;
   f16_t* nxt = w.e_b;
@@ -168,7 +169,8 @@ int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, floa
   g.c16 = w.e_exp;
   CHK(gemm(h, g, s));
   ProfScope ps(h, s, PK_GAP, (double)B * H * W * 1280 + 4.0 * B * 1280, (double)B * H * W * 1280 * 2);
-  HIPCHK(launch_gap_classifier(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
+  if (pooled) HIPCHK(launch_gap_pooled(w.e_exp, H * W, 1280, pooled, B, s));
+  else HIPCHK(launch_gap_classifier(w.e_exp, H * W, 1280, h->e_cls_w, h->e_cls_b, logits, score, score_stride, B, s));
   return 0;
 }
 

@@ -185,6 +185,20 @@ hipError_t launch_head_train_epoch(const float* feat, const int32_t* labels, int
                                    int32_t* step_correct, float* step_gnorm, float* grad_out, float* ws, hipStream_t s);
 hipError_t launch_head_eval(const float* feat, const int32_t* labels, int N, int batch, const float* params,
                             float* batch_loss, float* row_logits, float* ws, hipStream_t s);
+// the deployed EfficientNet classifier (Dropout(0.2)-Linear(1280,2)) on cached pooled rows (effnet_train.hip;
+// include/mmf_hip.h mmf_effcls_train_epoch / mmf_effcls_eval): one launch per epoch by one workgroup, parameters and
+// moments in registers; the eval one workgroup per batch; hipErrorInvalidValue on a bad R / N / batch / p_drop with
+// nothing launched
+constexpr int kEffClsParams = 2562;  // classifier.1.weight [2][1280] | classifier.1.bias [2]
+hipError_t launch_effcls_train_epoch(const float* feat, const int32_t* labels, int R, const int32_t* perm, int N,
+                                     const uint64_t* keep, float p_drop, int batch, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int step0, float* params,
+                                     float* exp_avg, float* exp_avg_sq, float* step_loss, int32_t* step_correct,
+                                     float* grad_out, hipStream_t s);
+hipError_t launch_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, const float* params,
+                              float* batch_loss, float* row_logits, hipStream_t s);
+// dst[b][y][x][c] = src[b][y][W - 1 - x][c] (uint8; mmf_hflip_u8)
+hipError_t launch_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, hipStream_t s);
 // the CLS rows the text heads read: out fp32 [B][768] = x[b * row_stride ..]; a sequence with ovf[b] != 0 (nullable)
 // gets a NaN row, as launch_text_heads gives it NaN logits
 hipError_t launch_text_cls_rows(const float* x, int row_stride, const int* ovf, float* out, int B, hipStream_t s);
@@ -261,6 +275,8 @@ hipError_t launch_se(const float* pool_part, int nchunks, float inv_hw, const fl
                      bool precise = false);  // precise: the fc1 SiLU in silu_precise form (fp32 tower)
 hipError_t launch_gap_classifier(const f16_t* x, int HW, int C, const float* w, const float* b, float* logits,
                                  float* score, int score_stride, int B, hipStream_t s);
+// the classifier's input row alone (mmf_effnet_pooled): pooled fp32 [B][C] = the ascending-pixel sum * (1 / HW)
+hipError_t launch_gap_pooled(const f16_t* x, int HW, int C, float* pooled, int B, hipStream_t s);
 hipError_t launch_fill_strided(float* p, int stride, int B, float v, hipStream_t s);
 // fused MBConv front: expand 1x1 (we fp16 [C][cin], be fp32, BN folded) + SiLU computed per input
 // tile into LDS, then the depthwise conv of launch_dwconv (same outputs, same pool partials)
@@ -314,3 +330,4 @@ hipError_t launch_dw32(const float* in, const float* w, const float* bias, float
 hipError_t launch_sum32(const float* x, int B, int HW, int C, int nchunks, float* part, hipStream_t s);
 hipError_t launch_gap32(const float* x, int HW, int C, const float* w, const float* b, float* logits, float* score,
                         int score_stride, int B, hipStream_t s);
+hipError_t launch_gap32_pooled(const float* x, int HW, int C, float* pooled, int B, hipStream_t s);

@@ -476,6 +476,33 @@ class Engine:
               "mmf_effnet_forward_f32")
         return lg, sc
 
+    def effnet_pooled(self, img):
+        """The row the deepfake classifier reads (mmf_effnet_pooled): the global average of the 7x7 head output,
+        float32 [B, 1280] on the device, by effnet_forward's launch sequence for the tower in use without the
+        classifier.  The run-time trap of the synchronous API paths (effnet_overflow): a non-finite row switches
+        the engine to the fp32 tower and the batch runs again."""
+        img = self._u8(img)
+        B = img.shape[0]
+        pooled = self._f32(B, 1280)
+
+        def run():
+            check(self.lib.mmf_effnet_pooled(self.h, ptr(img), B, ptr(pooled), stream_ptr()), "mmf_effnet_pooled")
+        run()
+        if self.effnet_overflow((pooled * 0).sum(1).cpu().numpy()):  # 0 or NaN per row
+            run()
+        return pooled
+
+    def hflip(self, img):
+        """A staged uint8 [B, H, W, C] window mirrored left-right (mmf_hflip_u8) into a new device tensor."""
+        t = self._tensor(img)
+        if not (t.dtype == torch.uint8 and t.dim() == 4 and t.numel() > 0):
+            raise ValueError(f"hflip: expected a non-empty uint8 [B, H, W, C] tensor, got {tuple(t.shape)} {t.dtype}")
+        t = t.to(self.device).contiguous()
+        out = torch.empty_like(t)
+        B, H, Wd, C = t.shape
+        check(self.lib.mmf_hflip_u8(ptr(t), ptr(out), B, H, Wd, C, stream_ptr()), "mmf_hflip_u8")
+        return out
+
     def clip_image(self, img):
         img = self._u8(img)
         e = self._f32(img.shape[0], 512)
@@ -643,6 +670,43 @@ class Engine:
         ws = self._head_train_ws(batch)
         check(self.lib.mmf_head_eval(ptr(feat), ptr(labels), N, int(batch), ptr(params), ptr(batch_loss),
                                      ptr(row_logits), ptr(ws), ws.numel(), stream_ptr()), "mmf_head_eval")
+        return batch_loss, row_logits
+
+    EFFCLS_PARAMS = 2562  # MMF_EFFCLS_PARAMS: classifier.1.weight [2][1280] | classifier.1.bias [2]
+
+    def effcls_train_epoch(self, feat, labels, perm, keep, p_drop: float, batch: int, lr: float, betas, eps: float,
+                           weight_decay: float, step0: int, params, exp_avg, exp_avg_sq, grad_out=None):
+        """One epoch of deepfake-classifier training in one launch (mmf_effcls_train_epoch): device tensors feat
+        float32 [R, 1280] and labels int32 [R] (the row bank), perm int32 [N] (bank rows), keep int64 [N, 20] (the
+        uint64 masks' bits) or None; params / exp_avg / exp_avg_sq float32 [2562], updated in place.  Returns
+        (step_loss float32 [nsteps], step_correct int32 [nsteps]) on the device; nothing is synchronised."""
+        R, N, P = int(labels.shape[0]), int(perm.shape[0]), self.EFFCLS_PARAMS
+        self._clip_train_check("effcls_train_epoch", (
+            ("feat", feat, torch.float32, 1280 * R, False), ("labels", labels, torch.int32, R, False),
+            ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, 20 * N, True),
+            ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
+            ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
+        nsteps = max(1, -(-N // max(1, int(batch))))
+        step_loss = self._f32(nsteps)
+        step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
+        check(self.lib.mmf_effcls_train_epoch(ptr(feat), ptr(labels), R, ptr(perm), N, ptr(keep), float(p_drop),
+                                              int(batch), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                              float(weight_decay), int(step0), ptr(params), ptr(exp_avg),
+                                              ptr(exp_avg_sq), ptr(step_loss), ptr(step_correct), ptr(grad_out),
+                                              stream_ptr()), "mmf_effcls_train_epoch")
+        return step_loss, step_correct
+
+    def effcls_eval(self, feat, labels, batch: int, params):
+        """validate's forward on cached pooled rows (mmf_effcls_eval): consecutive batches in row order ->
+        (batch_loss float32 [nbatches], row_logits float32 [R, 2]) on the device."""
+        R = int(labels.shape[0])
+        self._clip_train_check("effcls_eval", (
+            ("feat", feat, torch.float32, 1280 * R, False), ("labels", labels, torch.int32, R, False),
+            ("params", params, torch.float32, self.EFFCLS_PARAMS, False)))
+        nb = max(1, -(-R // max(1, int(batch))))
+        batch_loss, row_logits = self._f32(nb), self._f32(R, 2)
+        check(self.lib.mmf_effcls_eval(ptr(feat), ptr(labels), R, int(batch), ptr(params), ptr(batch_loss),
+                                       ptr(row_logits), stream_ptr()), "mmf_effcls_eval")
         return batch_loss, row_logits
 
     def vault_topk(self, q_unit: torch.Tensor, k: int = 5, thresh: float = 0.85, text_emb=None):

@@ -33,6 +33,10 @@ SIGNATURES = {
     "mmf_head_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "mmf_effnet_forward": (_I, [_P, _P, _I, _P, _P, _P]),
     "mmf_effnet_forward_f32": (_I, [_P, _P, _I, _P, _P, _P]),
+    "mmf_effnet_pooled": (_I, [_P, _P, _I, _P, _P]),
+    "mmf_hflip_u8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "mmf_effcls_train_epoch": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mmf_effcls_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mmf_clip_image": (_I, [_P, _P, _I, _P, _P]),
     "mmf_clip_text": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "mmf_clip_consistency": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
