@@ -25,6 +25,7 @@ tensor.
 from __future__ import annotations
 
 import argparse
+import functools
 import os
 import random
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -33,6 +34,8 @@ import numpy as np
 import torch
 
 from . import io_utils
+from . import training_common as TC
+from .training_common import _black, pack_keep  # pack_keep here: bool [N, 1280] -> uint64 [N, 20]
 
 BETAS, EPS, WEIGHT_DECAY = (0.9, 0.999), 1e-8, 0.0  # torch.optim.Adam defaults (train_cifake_forensics.py:334-337)
 P_DROP = 0.2                                        # the classifier's Dropout (misinfo_forensics.py:73)
@@ -82,10 +85,6 @@ def load_cifake_data(cifake_root: str, sample_per_label: int = 2500, seed: int =
 # ---------------------------------------------------------------------------------------------
 # cached features
 # ---------------------------------------------------------------------------------------------
-def _black():
-    return io_utils.Image.new("RGB", (224, 224), (0, 0, 0))
-
-
 def extract_image_features(forensics, image_paths: Sequence, flip: bool = False):
     """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
     the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
@@ -135,16 +134,7 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False)
 # ---------------------------------------------------------------------------------------------
 # the epoch plan
 # ---------------------------------------------------------------------------------------------
-def pack_keep(mask: np.ndarray) -> np.ndarray:
-    """bool [N, 1280] -> uint64 [N, 20]: word w bit j = input channel 64 w + j kept."""
-    m = np.asarray(mask, dtype=bool).reshape(-1, WORDS, 64).astype(np.uint64)
-    return (m << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
-
-
-def unpack_keep(keep: np.ndarray) -> np.ndarray:
-    """uint64 [N, 20] -> bool [N, 1280]."""
-    k = np.asarray(keep, np.uint64).reshape(-1, WORDS, 1)
-    return ((k >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(-1, WIDTH)
+unpack_keep = functools.partial(TC.unpack_keep, width=WIDTH)  # uint64 [N, 20] -> bool [N, 1280]
 
 
 def plan(N: int, batch_size: int, epochs: int, seed: int, flip: bool = True):
@@ -193,15 +183,7 @@ class ClassifierTrainer:
 
     @staticmethod
     def _data(feats, labels, what):
-        x = np.ascontiguousarray(np.asarray(feats, dtype=np.float32))
-        y = np.asarray(labels)
-        if x.ndim != 2 or x.shape[1] != WIDTH or len(x) == 0 or y.shape != (x.shape[0],):
-            raise ValueError(f"{what} features {x.shape} / labels {y.shape} must be [N, 1280] / [N], N >= 1")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{what} features must be finite")
-        if not np.isin(y, (0, 1)).all():
-            raise ValueError(f"{what} labels must be 0 or 1")
-        return x, y.astype(np.int32)
+        return TC.check_rows(what, (feats,), (WIDTH,), labels)
 
     def fit(self, train, train_labels, val, val_labels, checkpoint_path: Optional[str] = None,
             save_full_model: bool = False) -> List[dict]:
@@ -231,14 +213,8 @@ class ClassifierTrainer:
                                             EPS, self.weight_decay, step0, params, m, v)
             bl, lg = eng.effcls_eval(xv, yv_d, bs, params)
             step0 += spe
-            train_loss = float(sl.cpu().numpy().astype(np.float64).mean())  # running_loss / len(dataloader) (:224)
-            train_acc = float(100 * int(sc.cpu().numpy().astype(np.int64).sum()) / N)
-            val_loss = float(bl.cpu().numpy().astype(np.float64).mean())    # :270
-            if not (np.isfinite(train_loss) and np.isfinite(val_loss)):
-                raise FloatingPointError(f"epoch {epoch}: the loss is not finite")
-            lg = lg.cpu().numpy()
-            pred = (lg[:, 1] > lg[:, 0]).astype(np.int64)  # torch.max: a tie is class 0
-            val_acc = float(100 * int((pred == yv).sum()) / len(yv))
+            # train_cifake_forensics.py:224, :270
+            train_loss, train_acc, val_loss, val_acc, _ = TC.classifier_epoch_metrics(epoch, sl, sc, bl, lg, N, yv)
             history.append({"epoch": epoch, "train_loss": train_loss, "train_acc": train_acc, "val_loss": val_loss,
                             "val_acc": val_acc})
             if val_acc > best_acc:  # :372

@@ -26,6 +26,8 @@ import numpy as np
 import torch
 
 from . import io_utils
+from . import training_common as TC
+from .training_common import _black
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.AdamW defaults (train_clip_detective.py:345-349)
 N_VISUAL, N_TEXT = 512 * 768, 512 * 512
@@ -36,10 +38,6 @@ KEYS = ("visual_projection.weight", "text_projection.weight", "logit_scale")
 # ---------------------------------------------------------------------------------------------
 # cached features
 # ---------------------------------------------------------------------------------------------
-def _black():
-    return io_utils.Image.new("RGB", (224, 224), (0, 0, 0))
-
-
 def extract_features(forensics, texts: Sequence[str], image_paths: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     """What the frozen encoders of CLIPDetective give for every row of a GuardianCLIPDataset
     (train_clip_detective.py:39-73) -> (img_feat float32 [N, 768], txt_feat float32 [N, 512]), in
@@ -170,18 +168,13 @@ def optimizer_state_dict(exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, steps:
     """The state dict the reference's ``AdamW([p for p in model.parameters() if p.requires_grad])`` would hold
     with these moments and step count: built by a real AdamW over a CLIPDetective-shaped module, so the
     parameter order is the module's own and the dict loads into one."""
-    heads = _Heads()
-    m, v = split_heads(exp_avg), split_heads(exp_avg_sq)
-    named = [(n[len("clip."):], p) for n, p in heads.named_parameters()]
-    opt = torch.optim.AdamW([p for _, p in named], lr=initial_lr, weight_decay=weight_decay)
-    for name, p in named:
-        opt.state[p] = {"step": torch.tensor(float(steps)), "exp_avg": m[name].reshape(p.shape),
-                        "exp_avg_sq": v[name].reshape(p.shape)}
-    sd = opt.state_dict()
-    for gr in sd["param_groups"]:
-        gr["lr"] = lr
-        gr["initial_lr"] = initial_lr  # the key CosineAnnealingLR adds to the groups it schedules
-    return sd
+    named = [(n[len("clip."):], p) for n, p in _Heads().named_parameters()]
+
+    def in_module_order(flat):
+        parts = split_heads(flat)
+        return torch.cat([parts[n].reshape(-1) for n, _ in named])
+    return TC.adamw_state_dict([p for _, p in named], in_module_order(exp_avg), in_module_order(exp_avg_sq), steps, lr,
+                               initial_lr, weight_decay, device="cpu")
 
 
 class ClipProjectionTrainer:
@@ -197,13 +190,8 @@ class ClipProjectionTrainer:
 
     @staticmethod
     def _feats(feats, what):
-        img, txt = (np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in feats)
-        if img.ndim != 2 or txt.ndim != 2 or img.shape[1] != 768 or txt.shape[1] != 512 or len(img) != len(txt) \
-                or len(img) == 0:
-            raise ValueError(f"{what} features {img.shape} / {txt.shape} must be [N, 768] / [N, 512], N >= 1")
-        if not (np.isfinite(img).all() and np.isfinite(txt).all()):
-            raise ValueError(f"{what} features must be finite")
-        return img, txt
+        img, txt = feats
+        return TC.check_rows(what, (img, txt), (768, 512))
 
     def fit(self, train_feats, val_feats, val_labels, checkpoint_path: Optional[str] = None) -> List[dict]:
         f = self.forensics

@@ -681,10 +681,18 @@ int mmf_set_clip_projections(mmf_handle* h, const float* visual_f32, const float
 int64_t mmf_clip_train_ws_bytes(int batch) { return (int64_t)clip_train_ws_bytes(batch); }
 
 namespace {
-bool misaligned16(std::initializer_list<const void*> ps) {
+// the trainer entry points' shared checks: 0, or MMF_EINVAL with `what` in front
+int check_ws(const char* what, int64_t ws_bytes, size_t need) {
+  if (ws_bytes >= (int64_t)need) return 0;
+  return fail(MMF_EINVAL, "%s: ws of %lld bytes, %lld needed", what, (long long)ws_bytes, (long long)need);
+}
+// every pointer of ps on an `align`-byte boundary, the dropout masks (has_keep) on an 8-byte one; null pointers pass
+int check_aligned(const char* what, int align, std::initializer_list<const void*> ps, bool has_keep = false,
+                  const void* keep = nullptr) {
   uintptr_t a = 0;
   for (const void* p : ps) a |= (uintptr_t)p;
-  return (a & 15) != 0;
+  if (!(a & (uintptr_t)(align - 1)) && !((uintptr_t)keep & 7)) return 0;
+  return fail(MMF_EINVAL, "%s: pointers must be %d-byte aligned%s", what, align, has_keep ? " (keep: 8)" : "");
 }
 }  // namespace
 
@@ -696,11 +704,8 @@ int mmf_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, co
     return fail(MMF_EINVAL, "null argument");
   if (N < 1 || batch < 1 || batch > 64 || step0 < 0)
     return fail(MMF_EINVAL, "clip_train_epoch: N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0)", N, batch, step0);
-  if (ws_bytes < (int64_t)clip_train_ws_bytes(batch))
-    return fail(MMF_EINVAL, "clip_train_epoch: ws of %lld bytes, %lld needed", (long long)ws_bytes,
-                (long long)clip_train_ws_bytes(batch));
-  if (misaligned16({img_feat, txt_feat, params, exp_avg, exp_avg_sq, grad_out, ws}))
-    return fail(MMF_EINVAL, "clip_train_epoch: pointers must be 16-byte aligned");
+  CHK(check_ws("clip_train_epoch", ws_bytes, clip_train_ws_bytes(batch)));
+  CHK(check_aligned("clip_train_epoch", 16, {img_feat, txt_feat, params, exp_avg, exp_avg_sq, grad_out, ws}));
   HIPCHK(launch_clip_train_epoch(img_feat, txt_feat, N, perm, batch, lr, beta1, beta2, eps, weight_decay, max_norm,
                                  step0, params, exp_avg, exp_avg_sq, step_loss, step_gnorm, grad_out, (float*)ws,
                                  (hipStream_t)stream));
@@ -712,11 +717,8 @@ int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int 
   if (!img_feat || !txt_feat || !params || !batch_loss || !row_cos || !ws) return fail(MMF_EINVAL, "null argument");
   if (N < 1 || batch < 1 || batch > 64)
     return fail(MMF_EINVAL, "clip_contrastive_eval: N=%d (>= 1) batch=%d (1..64)", N, batch);
-  if (ws_bytes < (int64_t)clip_train_ws_bytes(batch))
-    return fail(MMF_EINVAL, "clip_contrastive_eval: ws of %lld bytes, %lld needed", (long long)ws_bytes,
-                (long long)clip_train_ws_bytes(batch));
-  if (misaligned16({img_feat, txt_feat, params, ws}))
-    return fail(MMF_EINVAL, "clip_contrastive_eval: pointers must be 16-byte aligned");
+  CHK(check_ws("clip_contrastive_eval", ws_bytes, clip_train_ws_bytes(batch)));
+  CHK(check_aligned("clip_contrastive_eval", 16, {img_feat, txt_feat, params, ws}));
   HIPCHK(launch_clip_contrastive_eval(img_feat, txt_feat, N, batch, params, batch_loss, row_cos, (float*)ws,
                                       (hipStream_t)stream));
   return 0;
@@ -735,11 +737,8 @@ int mmf_head_train_epoch(const float* feat, const int32_t* labels, int N, const 
   if (N < 1 || batch < 1 || batch > 64 || step0 < 0 || !(p_drop >= 0.f && p_drop < 1.f))
     return fail(MMF_EINVAL, "head_train_epoch: N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0) p_drop=%g ([0, 1))", N,
                 batch, step0, (double)p_drop);
-  if (ws_bytes < (int64_t)head_train_ws_bytes(batch))
-    return fail(MMF_EINVAL, "head_train_epoch: ws of %lld bytes, %lld needed", (long long)ws_bytes,
-                (long long)head_train_ws_bytes(batch));
-  if (misaligned16({feat, params, exp_avg, exp_avg_sq, grad_out, ws}) || ((uintptr_t)keep & 7))
-    return fail(MMF_EINVAL, "head_train_epoch: pointers must be 16-byte aligned (keep: 8)");
+  CHK(check_ws("head_train_epoch", ws_bytes, head_train_ws_bytes(batch)));
+  CHK(check_aligned("head_train_epoch", 16, {feat, params, exp_avg, exp_avg_sq, grad_out, ws}, true, keep));
   HIPCHK(launch_head_train_epoch(feat, labels, N, perm, keep, p_drop, batch, lr_steps, beta1, beta2, eps, weight_decay,
                                  max_norm, step0, params, exp_avg, exp_avg_sq, step_loss, step_correct, step_gnorm,
                                  grad_out, (float*)ws, (hipStream_t)stream));
@@ -750,10 +749,8 @@ int mmf_head_eval(const float* feat, const int32_t* labels, int N, int batch, co
                   float* row_logits, void* ws, int64_t ws_bytes, void* stream) {
   if (!feat || !labels || !params || !batch_loss || !row_logits || !ws) return fail(MMF_EINVAL, "null argument");
   if (N < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "head_eval: N=%d (>= 1) batch=%d (1..64)", N, batch);
-  if (ws_bytes < (int64_t)head_train_ws_bytes(batch))
-    return fail(MMF_EINVAL, "head_eval: ws of %lld bytes, %lld needed", (long long)ws_bytes,
-                (long long)head_train_ws_bytes(batch));
-  if (misaligned16({feat, params, ws})) return fail(MMF_EINVAL, "head_eval: pointers must be 16-byte aligned");
+  CHK(check_ws("head_eval", ws_bytes, head_train_ws_bytes(batch)));
+  CHK(check_aligned("head_eval", 16, {feat, params, ws}));
   HIPCHK(launch_head_eval(feat, labels, N, batch, params, batch_loss, row_logits, (float*)ws, (hipStream_t)stream));
   return 0;
 }
@@ -785,10 +782,8 @@ int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, cons
   if (R < 1 || N < 1 || batch < 1 || batch > 64 || step0 < 0 || !(p_drop >= 0.f && p_drop < 1.f))
     return fail(MMF_EINVAL, "effcls_train_epoch: R=%d N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0) p_drop=%g ([0, 1))",
                 R, N, batch, step0, (double)p_drop);
-  if (((uintptr_t)feat | (uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)step_loss |
-       (uintptr_t)grad_out | (uintptr_t)labels | (uintptr_t)perm | (uintptr_t)step_correct) & 3 ||
-      ((uintptr_t)keep & 7))
-    return fail(MMF_EINVAL, "effcls_train_epoch: pointers must be 4-byte aligned (keep: 8)");
+  CHK(check_aligned("effcls_train_epoch", 4,
+                    {feat, params, exp_avg, exp_avg_sq, step_loss, grad_out, labels, perm, step_correct}, true, keep));
   HIPCHK(launch_effcls_train_epoch(feat, labels, R, perm, N, keep, p_drop, batch, lr, beta1, beta2, eps, weight_decay,
                                    step0, params, exp_avg, exp_avg_sq, step_loss, step_correct, grad_out,
                                    (hipStream_t)stream));
@@ -799,8 +794,7 @@ int mmf_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, 
                     float* row_logits, void* stream) {
   if (!feat || !labels || !params || !batch_loss || !row_logits) return fail(MMF_EINVAL, "null argument");
   if (R < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "effcls_eval: R=%d (>= 1) batch=%d (1..64)", R, batch);
-  if (((uintptr_t)feat | (uintptr_t)labels | (uintptr_t)params | (uintptr_t)batch_loss | (uintptr_t)row_logits) & 3)
-    return fail(MMF_EINVAL, "effcls_eval: pointers must be 4-byte aligned");
+  CHK(check_aligned("effcls_eval", 4, {feat, labels, params, batch_loss, row_logits}));
   HIPCHK(launch_effcls_eval(feat, labels, R, batch, params, batch_loss, row_logits, (hipStream_t)stream));
   return 0;
 }

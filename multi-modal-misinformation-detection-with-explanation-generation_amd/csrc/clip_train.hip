@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "train_common.h"
 
 namespace {
 
@@ -45,19 +46,6 @@ constexpr size_t W_DE = W_SC + 4;                            // [2][64][512] dL/
 constexpr size_t W_PART = W_DE + 2 * CT_BMAX * CT_D;         // [640]        per-block sums of squares
 constexpr size_t W_G = W_PART + CT_NBLK;                     // [655,360 + 4] the unclipped gradient
 constexpr size_t W_END = W_G + CT_NW + 4;
-
-// sum of 256 values, one per thread, by a fixed tree (s = 128, 64, ..., 1); the result on every thread
-MMF_DEV float block_tree_sum(float v, float* red, int tid) {
-  __syncthreads();  // earlier readers of red are done
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (tid < s) red[tid] = red[tid] + red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // ---- 1a. e = P W^T: grid (32 blocks of 16 outputs, 2 towers), 256 threads = 16 outputs x 16 rows ----
 // K runs in tiles of 256 staged in LDS by coalesced 16-byte loads (W rows are 2-3 KB apart: a thread walking its
@@ -298,20 +286,10 @@ __global__ __launch_bounds__(256) void clip_wgrad_kernel(int rows, float* ws) {
   if (tid == 0) ws[W_PART + blockIdx.x] = tot;
 }
 
-struct CtAdam {
-  float decay, w1, b2, w2, eps, step_size, bc2s, max_norm;
-};
-
-MMF_DEV void ct_adam1(const CtAdam& A, float g, float& p, float& m, float& v) {
-  p = p * A.decay;
-  m = m + A.w1 * (g - m);
-  v = v * A.b2 + A.w2 * (g * g);
-  p = p - A.step_size * (m / (sqrtf(v) / A.bc2s + A.eps));
-}
-
 // ---- 5. total norm, clip coefficient, AdamW: 640 blocks of 256 threads ----
-__global__ __launch_bounds__(256) void clip_adamw_kernel(CtAdam A, float* params, float* exp_avg, float* exp_avg_sq,
-                                                         const float* ws, float* gnorm_out, float* grad_out) {
+__global__ __launch_bounds__(256) void clip_adamw_kernel(AdamScalars A, float max_norm, float* params, float* exp_avg,
+                                                         float* exp_avg_sq, const float* ws, float* gnorm_out,
+                                                         float* grad_out) {
   __shared__ float red[256];
   const int tid = threadIdx.x;
   const int flat = blockIdx.x * CT_BLK + tid * 4;
@@ -326,12 +304,12 @@ __global__ __launch_bounds__(256) void clip_adamw_kernel(CtAdam A, float* params
   if (tid + 512 < CT_NBLK) s += ws[W_PART + tid + 512];
   const float gs = ws[W_SC + 1];
   const float norm = sqrtf(fmaf(gs, gs, block_tree_sum(s, red, tid)));
-  const float c = fminf(A.max_norm / (norm + 1e-6f), 1.0f);  // clip_grad_norm_: clamped at 1, always applied
+  const float c = fminf(max_norm / (norm + 1e-6f), 1.0f);  // clip_grad_norm_: clamped at 1, always applied
   g.x *= c; g.y *= c; g.z *= c; g.w *= c;
-  ct_adam1(A, g.x, p.x, m.x, v.x);
-  ct_adam1(A, g.y, p.y, m.y, v.y);
-  ct_adam1(A, g.z, p.z, m.z, v.z);
-  ct_adam1(A, g.w, p.w, m.w, v.w);
+  adamw_update(A, g.x, p.x, m.x, v.x);
+  adamw_update(A, g.y, p.y, m.y, v.y);
+  adamw_update(A, g.z, p.z, m.z, v.z);
+  adamw_update(A, g.w, p.w, m.w, v.w);
   *reinterpret_cast<float4*>(params + flat) = p;
   *reinterpret_cast<float4*>(exp_avg + flat) = m;
   *reinterpret_cast<float4*>(exp_avg_sq + flat) = v;
@@ -339,7 +317,7 @@ __global__ __launch_bounds__(256) void clip_adamw_kernel(CtAdam A, float* params
   if (blockIdx.x == 0 && tid == 0) {  // logit_scale, and the step's norm
     float ps = params[CT_NW], ms = exp_avg[CT_NW], vs = exp_avg_sq[CT_NW];
     const float gc = gs * c;
-    ct_adam1(A, gc, ps, ms, vs);
+    adamw_update(A, gc, ps, ms, vs);
     params[CT_NW] = ps;
     exp_avg[CT_NW] = ms;
     exp_avg_sq[CT_NW] = vs;
@@ -355,17 +333,6 @@ __global__ __launch_bounds__(256) void f32_to_f16_kernel(const float* src, f16_t
   *reinterpret_cast<uint2*>(dst + (size_t)i * 4) = make_uint2(pack2h(v.x, v.y), pack2h(v.z, v.w));
 }
 
-// b^n by squaring, a function of (b, n) alone
-double ct_ipow(double b, int n) {
-  double r = 1.0;
-  while (n > 0) {
-    if (n & 1) r *= b;
-    b *= b;
-    n >>= 1;
-  }
-  return r;
-}
-
 }  // namespace
 
 size_t clip_train_ws_bytes(int batch) { return (batch < 1 || batch > CT_BMAX) ? 0 : W_END * sizeof(float); }
@@ -378,18 +345,15 @@ hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat,
   const int nsteps = (N + batch - 1) / batch;
   for (int st = 0; st < nsteps; ++st) {
     const int pos0 = st * batch, rows = std::min(batch, N - pos0);
-    const int step = step0 + st + 1;
-    const double bc1 = 1.0 - ct_ipow(beta1, step), bc2 = 1.0 - ct_ipow(beta2, step);
-    const CtAdam A{(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                   (float)eps, (float)(lr / bc1), (float)std::sqrt(bc2), (float)max_norm};
+    const AdamScalars A = adam_scalars(lr, beta1, beta2, eps, weight_decay, step0 + st + 1);
     hipLaunchKernelGGL(clip_project_kernel, dim3(CT_D / PJ_J, 2), dim3(256), 0, s, img_feat, txt_feat, N, perm, pos0,
                        rows, params, ws);
     hipLaunchKernelGGL(clip_normalise_kernel, dim3(rows, 2), dim3(256), 0, s, ws);
     hipLaunchKernelGGL(clip_logits_kernel, dim3(1), dim3(256), 0, s, rows, params, ws, step_loss + st, nullptr, 1);
     hipLaunchKernelGGL(clip_embgrad_kernel, dim3(rows, 2), dim3(128), 0, s, rows, ws);
     hipLaunchKernelGGL(clip_wgrad_kernel, dim3(CT_NBLK), dim3(256), 0, s, rows, ws);
-    hipLaunchKernelGGL(clip_adamw_kernel, dim3(CT_NBLK), dim3(256), 0, s, A, params, exp_avg, exp_avg_sq, ws,
-                       step_gnorm + st, st == nsteps - 1 ? grad_out : nullptr);
+    hipLaunchKernelGGL(clip_adamw_kernel, dim3(CT_NBLK), dim3(256), 0, s, A, (float)max_norm, params, exp_avg,
+                       exp_avg_sq, ws, step_gnorm + st, st == nsteps - 1 ? grad_out : nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

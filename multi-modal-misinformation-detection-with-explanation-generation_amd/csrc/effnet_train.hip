@@ -25,6 +25,7 @@
 // workgroup per batch.  Loop bounds come from N and batch only; no flags, spin-waits or atomics.
 #include "common.h"
 #include "kernels.h"
+#include "train_common.h"
 
 namespace {
 
@@ -36,17 +37,6 @@ constexpr int EC_SLOTS = 2 * EC_KT + 1;  // 10 weights + (threads 0, 1) a bias
 constexpr int EC_EB = 64;          // the largest batch
 static_assert(kEffClsParams == EC_P, "effnet_train: parameter count");
 
-// b^n by squaring, a function of (b, n) alone
-MMF_DEV double ec_ipow(double b, int n) {
-  double r = 1.0;
-  while (n > 0) {
-    if (n & 1) r *= b;
-    b *= b;
-    n >>= 1;
-  }
-  return r;
-}
-
 struct EcArgs {
   const float* feat; const int32_t* labels; int R;
   const int32_t* perm; int N; const uint64_t* keep; float scale; int batch;
@@ -54,17 +44,8 @@ struct EcArgs {
   float *params, *exp_avg, *exp_avg_sq, *step_loss; int32_t* step_correct; float* grad_out;
 };
 
-// a chunk of the epoch: rows c0 .. c0 + 15 of minibatch st
-struct EcChunk { int st, c0; };
+using EcWalk = EpochWalk<EC_RC>;
 
-MMF_DEV int ec_rows(const EcArgs& A, int st) { return min(A.batch, A.N - st * A.batch); }
-MMF_DEV EcChunk ec_next(const EcArgs& A, EcChunk c) {
-  return (c.c0 + EC_RC < ec_rows(A, c.st)) ? EcChunk{c.st, c.c0 + EC_RC} : EcChunk{c.st + 1, 0};
-}
-// position in the epoch order of row r of chunk c, -1 where there is none
-MMF_DEV int ec_pos(const EcArgs& A, EcChunk c, int r, int nsteps) {
-  return (c.st < nsteps && c.c0 + r < ec_rows(A, c.st)) ? c.st * A.batch + c.c0 + r : -1;
-}
 // the raw permutation entry at pos (0 for pos -1), and the clamped bank row it names (-1 for pos -1): two steps, so
 // that the entry can be loaded a chunk before anything reads it
 MMF_DEV int ec_entry(const EcArgs& A, int pos) { return pos < 0 ? 0 : A.perm[pos]; }
@@ -78,7 +59,7 @@ MMF_DEV bool ec_live(int q, int tid) { return q < 2 * EC_KT || tid < 2; }
 
 // thread tid's five columns of the rows of chunk c (bank rows src[]) and the 32-bit mask words that hold their keep
 // bits, both RAW: nothing here reads a loaded value, so the loads stay in flight until ec_apply
-MMF_DEV void ec_fetch(const EcArgs& A, EcChunk c, const int (&src)[EC_RC], int nsteps, int tid,
+MMF_DEV void ec_fetch(const EcArgs& A, EcWalk wk, Chunk c, const int (&src)[EC_RC], int tid,
                       float (&x)[EC_RC][EC_KT], uint32_t (&kw)[EC_RC][EC_KT]) {
   const int lane = tid & 63, wave = tid >> 6;
   const uint32_t* keep32 = reinterpret_cast<const uint32_t*>(A.keep);
@@ -90,7 +71,7 @@ MMF_DEV void ec_fetch(const EcArgs& A, EcChunk c, const int (&src)[EC_RC], int n
       for (int k = 0; k < EC_KT; ++k) x[r][k] = row[256 * k];
       if (A.keep) {
         // column tid + 256 k = 64-bit word wave + 4 k, bit lane = 32-bit word 2 (wave + 4 k) + lane / 32, bit lane % 32
-        const uint32_t* w = keep32 + (size_t)ec_pos(A, c, r, nsteps) * (EC_K / 32) + 2 * wave + (lane >> 5);
+        const uint32_t* w = keep32 + (size_t)wk.pos(c, r) * (EC_K / 32) + 2 * wave + (lane >> 5);
 #pragma unroll
         for (int k = 0; k < EC_KT; ++k) kw[r][k] = w[8 * k];
       }
@@ -111,19 +92,6 @@ MMF_DEV void ec_apply(const EcArgs& A, int tid, const float (&x)[EC_RC][EC_KT], 
       xd[r][k] = !A.keep ? x[r][k] : (((kw[r][k] >> bit) & 1) ? x[r][k] * A.scale : 0.f);
 }
 
-// one row's loss, correctness and dL/dlogits * rows from its two logits
-struct EcRow { float loss, cor, d0, d1; };
-MMF_DEV EcRow ec_row(float l0, float l1, int lab) {
-  const float m = fmaxf(l0, l1);
-  const float e0 = expf(l0 - m), e1 = expf(l1 - m), den = e0 + e1;
-  EcRow o;
-  o.loss = (m + logf(den)) - (lab ? l1 : l0);
-  o.cor = ((l1 > l0) == (lab != 0)) ? 1.f : 0.f;  // a tie is class 0 (torch.max)
-  o.d0 = e0 / den - (lab ? 0.f : 1.f);
-  o.d1 = e1 / den - (lab ? 1.f : 0.f);
-  return o;
-}
-
 __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
   __shared__ float s_red[4][EC_RC][2];  // per wave, the wave's sum of the partial logits of (row, class)
   __shared__ float s_dl[EC_RC][2], s_loss[EC_RC], s_cor[EC_RC], s_b[2];
@@ -141,6 +109,7 @@ __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
   if (tid < 2) s_b[tid] = pv[2 * EC_KT];
 
   const int nsteps = (A.N + A.batch - 1) / A.batch;
+  const EcWalk wk{A.N, A.batch, nsteps};
   // xn, kn: the next chunk's rows and mask words, raw; pe: the raw permutation entries of the chunk after it; thread
   // r < 16 also holds row r's raw label (labn) and its own entry of the chunk after (mype)
   float xn[EC_RC][EC_KT];
@@ -151,28 +120,29 @@ __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
 #pragma unroll
     for (int k = 0; k < EC_KT; ++k) kn[r][k] = 0u;
   {
-    const EcChunk first{0, 0}, second = ec_next(A, first);
+    const Chunk first{0, 0}, second = wk.next(first);
 #pragma unroll
     for (int r = 0; r < EC_RC; ++r) {
-      const int pos = ec_pos(A, first, r, nsteps);
+      const int pos = wk.pos(first, r);
       src[r] = ec_src(A, pos, ec_entry(A, pos));
     }
-    ec_fetch(A, first, src, nsteps, tid, xn, kn);
+    ec_fetch(A, wk, first, src, tid, xn, kn);
     if (tid < EC_RC) {
-      const int pos = ec_pos(A, first, tid, nsteps), s0 = ec_src(A, pos, ec_entry(A, pos));
+      const int pos = wk.pos(first, tid), s0 = ec_src(A, pos, ec_entry(A, pos));
       if (s0 >= 0) labn = A.labels[s0];
-      mype = ec_entry(A, ec_pos(A, second, tid, nsteps));
+      mype = ec_entry(A, wk.pos(second, tid));
     }
 #pragma unroll
-    for (int r = 0; r < EC_RC; ++r) pe[r] = ec_entry(A, ec_pos(A, second, r, nsteps));
+    for (int r = 0; r < EC_RC; ++r) pe[r] = ec_entry(A, wk.pos(second, r));
   }
-  const float w1 = (float)(1.0 - A.beta1), b2 = (float)A.beta2, w2 = (float)(1.0 - A.beta2), epsf = (float)A.eps,
-              wdf = (float)A.wd;
-  const bool decay = A.wd != 0.0;
   for (int st = 0; st < nsteps; ++st) {
     const int rows = min(A.batch, A.N - st * A.batch);
     const float inv_rows = 1.0f / (float)rows;
     float loss_sum = 0.f, cor_sum = 0.f;  // thread 0
+    // the step's optimizer scalars: a function of the hyperparameters and the global step number alone
+    const AdamScalars ad = adam_scalars(A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step0 + st + 1);
+    const float wdf = (float)A.wd;
+    const bool decay = A.wd != 0.0;
 #pragma unroll
     for (int q = 0; q < EC_SLOTS; ++q) g[q] = 0.f;
 
@@ -182,17 +152,17 @@ __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
       ec_apply(A, tid, xn, kn, xc);
       const int labc = labn & 1;
       // the next chunk's rows (its entries arrived a chunk ago), then the entries of the chunk after it: all raw
-      const EcChunk nxt = ec_next(A, EcChunk{st, c0}), nn = ec_next(A, nxt);
+      const Chunk nxt = wk.next(Chunk{st, c0}), nn = wk.next(nxt);
 #pragma unroll
-      for (int r = 0; r < EC_RC; ++r) src[r] = ec_src(A, ec_pos(A, nxt, r, nsteps), pe[r]);
-      ec_fetch(A, nxt, src, nsteps, tid, xn, kn);
+      for (int r = 0; r < EC_RC; ++r) src[r] = ec_src(A, wk.pos(nxt, r), pe[r]);
+      ec_fetch(A, wk, nxt, src, tid, xn, kn);
       if (tid < EC_RC) {
-        const int s1 = ec_src(A, ec_pos(A, nxt, tid, nsteps), mype);
+        const int s1 = ec_src(A, wk.pos(nxt, tid), mype);
         if (s1 >= 0) labn = A.labels[s1];
-        mype = ec_entry(A, ec_pos(A, nn, tid, nsteps));
+        mype = ec_entry(A, wk.pos(nn, tid));
       }
 #pragma unroll
-      for (int r = 0; r < EC_RC; ++r) pe[r] = ec_entry(A, ec_pos(A, nn, r, nsteps));
+      for (int r = 0; r < EC_RC; ++r) pe[r] = ec_entry(A, wk.pos(nn, r));
 
       // partial logits: the thread's chain, then the wave's tree -- all 16 rows level by level (a missing row is
       // zeros), so the 32 butterflies overlap instead of queueing behind each other's cross-lane latency
@@ -226,9 +196,9 @@ __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
         const int r = tid;
         const float l0 = (((s_red[0][r][0] + s_red[1][r][0]) + s_red[2][r][0]) + s_red[3][r][0]) + s_b[0];
         const float l1 = (((s_red[0][r][1] + s_red[1][r][1]) + s_red[2][r][1]) + s_red[3][r][1]) + s_b[1];
-        const EcRow o = ec_row(l0, l1, labc);
+        const CeRow o = ce_row(l0, l1, labc);
         s_loss[r] = o.loss;
-        s_cor[r] = o.cor;
+        s_cor[r] = o.hit ? 1.f : 0.f;
         s_dl[r][0] = o.d0 * inv_rows;
         s_dl[r][1] = o.d1 * inv_rows;
       }
@@ -250,16 +220,9 @@ __global__ __launch_bounds__(256) void effcls_train_epoch_kernel(EcArgs A) {
     }
 
     // torch.optim.Adam (single-tensor form): L2 decay into the gradient, bias correction by the global step
-    const int step = A.step0 + st + 1;
-    const double bc1 = 1.0 - ec_ipow(A.beta1, step), bc2 = 1.0 - ec_ipow(A.beta2, step);
-    const float step_size = (float)(A.lr / bc1), bc2s = (float)sqrt(bc2);
 #pragma unroll
     for (int q = 0; q < EC_SLOTS; ++q) {
-      const float gd = decay ? fmaf(wdf, pv[q], g[q]) : g[q];
-      mv[q] = mv[q] + w1 * (gd - mv[q]);
-      vv[q] = vv[q] * b2 + w2 * (gd * gd);
-      const float denom = sqrtf(vv[q]) / bc2s + epsf;
-      pv[q] = pv[q] - step_size * (mv[q] / denom);
+      adam_update(ad, decay ? fmaf(wdf, pv[q], g[q]) : g[q], pv[q], mv[q], vv[q]);
     }
     // (the readers of s_b of this step passed the chunk's second barrier; the next readers wait for the next first one)
     if (tid < 2) s_b[tid] = pv[2 * EC_KT];
@@ -320,7 +283,7 @@ __global__ __launch_bounds__(256) void effcls_eval_kernel(const float* __restric
     const float l1 = (((s_red[0][r][1] + s_red[1][r][1]) + s_red[2][r][1]) + s_red[3][r][1]) + params[2 * EC_K + 1];
     row_logits[(size_t)(r0 + r) * 2] = l0;
     row_logits[(size_t)(r0 + r) * 2 + 1] = l1;
-    s_loss[r] = ec_row(l0, l1, labels[r0 + r] & 1).loss;
+    s_loss[r] = ce_row(l0, l1, labels[r0 + r] & 1).loss;
   }
   __syncthreads();
   if (tid == 0) {

@@ -17,6 +17,7 @@
 // chains continue across chunks, so the chunking does not change the order.
 #include "common.h"
 #include "kernels.h"
+#include "train_common.h"
 
 namespace {
 
@@ -57,17 +58,6 @@ MMF_DEV FtSlot ft_slot(int p) {
   return {O_ONE, O_ONE, 0, O_ONE, 0};  // no parameter: reads 1.0f, stores nothing
 }
 
-// b^n by squaring, a function of (b, n) alone
-MMF_DEV double ft_ipow(double b, int n) {
-  double r = 1.0;
-  while (n > 0) {
-    if (n & 1) r *= b;
-    b *= b;
-    n >>= 1;
-  }
-  return r;
-}
-
 struct FtArgs {
   const float* scores5; const int32_t* labels; int N;
   const int32_t* perm; const uint64_t* keep; float scale; int batch;
@@ -75,19 +65,9 @@ struct FtArgs {
   float *params, *exp_avg, *exp_avg_sq, *step_loss; int32_t* step_correct; float* grad_out;
 };
 
-// a chunk of the epoch: rows c0 .. c0 + 63 of minibatch st
-struct FtChunk { int st, c0; };
 // one row's inputs, fetched ahead of the chunk that uses them
 struct FtRow { float x[5]; int lab; uint32_t klo, khi; };
 
-MMF_DEV int ft_rows(const FtArgs& A, int st) { return min(A.batch, A.N - st * A.batch); }
-MMF_DEV FtChunk ft_next(const FtArgs& A, FtChunk c) {
-  return (c.c0 + FT_RC < ft_rows(A, c.st)) ? FtChunk{c.st, c.c0 + FT_RC} : FtChunk{c.st + 1, 0};
-}
-// position in the epoch order of row r of chunk c, -1 where there is none
-MMF_DEV int ft_pos(const FtArgs& A, FtChunk c, int r, int nsteps) {
-  return (c.st < nsteps && c.c0 + r < ft_rows(A, c.st)) ? c.st * A.batch + c.c0 + r : -1;
-}
 // the (clamped) permutation entry at pos, -1 for pos -1
 MMF_DEV int ft_src(const FtArgs& A, int pos) { return pos < 0 ? -1 : min(max(A.perm[pos], 0), A.N - 1); }
 MMF_DEV void ft_fetch(const FtArgs& A, int src, int pos, FtRow& d) {
@@ -121,18 +101,17 @@ __global__ __launch_bounds__(256) void fusion_train_epoch_kernel(FtArgs A) {
     if (tid + 256 * s < FT_P) S[sl[s].loc] = pv[s];
 
   const int nsteps = (A.N + A.batch - 1) / A.batch;
+  const EpochWalk<FT_RC> wk{A.N, A.batch, nsteps};
   // wave 0, thread r: row r of the current chunk in `row`, the next chunk's permutation entry in `src1`
   FtRow row = {};
   int src1 = -1, pos1 = -1;
   if (tid < FT_RC) {
-    const FtChunk first{0, 0};
-    const int pos = ft_pos(A, first, tid, nsteps);
+    const Chunk first{0, 0};
+    const int pos = wk.pos(first, tid);
     ft_fetch(A, ft_src(A, pos), pos, row);
-    pos1 = ft_pos(A, ft_next(A, first), tid, nsteps);
+    pos1 = wk.pos(wk.next(first), tid);
     src1 = ft_src(A, pos1);
   }
-  const float decay = (float)(1.0 - A.lr * A.wd), w1 = (float)(1.0 - A.beta1), b2 = (float)A.beta2,
-              w2 = (float)(1.0 - A.beta2), epsf = (float)A.eps;
   for (int st = 0; st < nsteps; ++st) {
     const int pos0 = st * A.batch;
     const int rows = min(A.batch, A.N - pos0);
@@ -153,9 +132,9 @@ __global__ __launch_bounds__(256) void fusion_train_epoch_kernel(FtArgs A) {
           S[O_KEEP + tid * 2] = __uint_as_float(row.klo);
           S[O_KEEP + tid * 2 + 1] = __uint_as_float(row.khi);
         }
-        const FtChunk nxt = ft_next(A, FtChunk{st, c0});
+        const Chunk nxt = wk.next(Chunk{st, c0});
         ft_fetch(A, src1, pos1, row);
-        pos1 = ft_pos(A, ft_next(A, nxt), tid, nsteps);
+        pos1 = wk.pos(wk.next(nxt), tid);
         src1 = ft_src(A, pos1);
       }
       __syncthreads();
@@ -188,12 +167,11 @@ __global__ __launch_bounds__(256) void fusion_train_epoch_kernel(FtArgs A) {
           l0 = fmaf(S[O_W5 + o], S[O_H2 + r * 32 + o], l0);
           l1 = fmaf(S[O_W5 + 32 + o], S[O_H2 + r * 32 + o], l1);
         }
-        const float m = fmaxf(l0, l1);
-        const float e0 = expf(l0 - m), e1 = expf(l1 - m), den = e0 + e1;
-        S[O_LOSS + r] = (m + logf(den)) - (lab ? l1 : l0);
-        S[O_COR + r] = ((l1 > l0) == (lab != 0)) ? 1.f : 0.f;  // a tie is class 0 (torch.max)
-        S[O_DL + r * 2] = (e0 / den - (lab ? 0.f : 1.f)) * inv_rows;
-        S[O_DL + r * 2 + 1] = (e1 / den - (lab ? 1.f : 0.f)) * inv_rows;
+        const CeRow o = ce_row(l0, l1, lab);
+        S[O_LOSS + r] = o.loss;
+        S[O_COR + r] = o.hit ? 1.f : 0.f;
+        S[O_DL + r * 2] = o.d0 * inv_rows;
+        S[O_DL + r * 2 + 1] = o.d1 * inv_rows;
       }
       __syncthreads();
       // dL/dz2 = (dlogits W5) * [h2 > 0]: item (row r, unit k)
@@ -224,19 +202,12 @@ __global__ __launch_bounds__(256) void fusion_train_epoch_kernel(FtArgs A) {
     }
 
     // AdamW (torch.optim.AdamW, single-tensor form), bias correction by the global step
-    const int step = A.step0 + st + 1;
-    const double bc1 = 1.0 - ft_ipow(A.beta1, step), bc2 = 1.0 - ft_ipow(A.beta2, step);
-    const float step_size = (float)(A.lr / bc1), bc2s = (float)sqrt(bc2);
+    const AdamScalars ad = adam_scalars(A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step0 + st + 1);
     // (no barrier: since the last one every thread reads activations only, never the parameters)
 #pragma unroll
     for (int s = 0; s < FT_SLOTS; ++s) {
-      float p = pv[s] * decay;
-      mv[s] = mv[s] + w1 * (g[s] - mv[s]);
-      vv[s] = vv[s] * b2 + w2 * (g[s] * g[s]);
-      const float denom = sqrtf(vv[s]) / bc2s + epsf;
-      p = p - step_size * (mv[s] / denom);
-      pv[s] = p;
-      if (tid + 256 * s < FT_P) S[sl[s].loc] = p;
+      adamw_update(ad, g[s], pv[s], mv[s], vv[s]);
+      if (tid + 256 * s < FT_P) S[sl[s].loc] = pv[s];
     }
     if (tid == 0) {
       A.step_loss[st] = loss_sum * inv_rows;

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "train_common.h"
 
 namespace {
 
@@ -51,19 +52,6 @@ constexpr size_t W_DP = W_PRE + HT_BMAX * HT_H;            // [64][256] dL/dpre
 constexpr size_t W_PART = W_DP + HT_BMAX * HT_H;           // [192 + 1 (+3)] per-block sums of squares, the tail's
 constexpr size_t W_G = W_PART + HT_NBLK + 4;               // [197,378 (+2)] the unclipped gradient
 constexpr size_t W_END = W_G + kHeadTrainParams + 2;
-
-// sum of 256 values, one per thread, by a fixed tree (s = 128, 64, ..., 1); the result on every thread
-MMF_DEV float ht_tree_sum(float v, float* red, int tid) {
-  __syncthreads();  // earlier readers of red are done
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (tid < s) red[tid] = red[tid] + red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // ---- 1. pre = X W1^T + b1: 16 blocks of 16 hidden units, 256 threads = 16 units x 16 rows ----
 // K runs in tiles of 256 staged in LDS by coalesced 16-byte loads (W1 rows are 3 KB apart: a thread walking its own
@@ -169,15 +157,12 @@ __global__ __launch_bounds__(256) void head_mid_kernel(const int32_t* labels, in
   __syncthreads();
   if (tid < rows) {
     const float l0 = lg[tid * 2], l1 = lg[tid * 2 + 1];
-    const int y = lab[tid];
-    const float m = fmaxf(l0, l1);
-    const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-    const float se = e0 + e1;
-    rloss[tid] = (m + logf(se)) - (y ? l1 : l0);
-    hit[tid] = ((l1 > l0) ? 1 : 0) == y;
+    const CeRow o = ce_row(l0, l1, lab[tid]);
+    rloss[tid] = o.loss;
+    hit[tid] = o.hit;
     const float inv = 1.0f / (float)rows;
-    dl[tid * 2] = (e0 / se - (y ? 0.f : 1.f)) * inv;
-    dl[tid * 2 + 1] = (e1 / se - (y ? 1.f : 0.f)) * inv;
+    dl[tid * 2] = o.d0 * inv;
+    dl[tid * 2 + 1] = o.d1 * inv;
     if (!train) {
       row_logits[(size_t)tid * 2] = l0;
       row_logits[(size_t)tid * 2 + 1] = l1;
@@ -213,7 +198,7 @@ __global__ __launch_bounds__(256) void head_mid_kernel(const int32_t* labels, in
   G[HT_B1 + tid] = db1;
   G[HT_W2 + tid] = g20;
   G[HT_W2 + HT_H + tid] = g21;
-  float tot = ht_tree_sum(fmaf(g21, g21, fmaf(g20, g20, db1 * db1)), red, tid);
+  float tot = block_tree_sum(fmaf(g21, g21, fmaf(g20, g20, db1 * db1)), red, tid);
   if (tid == 0) {
     float b0 = 0.f, b1 = 0.f;
     for (int r = 0; r < rows; ++r) {
@@ -258,24 +243,14 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(int rows, float* ws) {
   }
   *reinterpret_cast<float4*>(ws + W_G + flat) = g;
   const float sq = fmaf(g.w, g.w, fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)));
-  const float tot = ht_tree_sum(sq, red, tid);
+  const float tot = block_tree_sum(sq, red, tid);
   if (tid == 0) ws[W_PART + blockIdx.x] = tot;
 }
 
-struct HtAdam {
-  float decay, w1, b2, w2, eps, step_size, bc2s, max_norm;
-};
-
-MMF_DEV void ht_adam1(const HtAdam& A, float g, float& p, float& m, float& v) {
-  p = p * A.decay;
-  m = m + A.w1 * (g - m);
-  v = v * A.b2 + A.w2 * (g * g);
-  p = p - A.step_size * (m / (sqrtf(v) / A.bc2s + A.eps));
-}
-
 // ---- 4. total norm, clip coefficient, AdamW: 192 blocks of 1,024 elements + 1 block for the 770 tail elements ----
-__global__ __launch_bounds__(256) void head_adamw_kernel(HtAdam A, float* params, float* exp_avg, float* exp_avg_sq,
-                                                         const float* ws, float* gnorm_out, float* grad_out) {
+__global__ __launch_bounds__(256) void head_adamw_kernel(AdamScalars A, float max_norm, float* params, float* exp_avg,
+                                                         float* exp_avg_sq, const float* ws, float* gnorm_out,
+                                                         float* grad_out) {
   __shared__ float red[256];
   const int tid = threadIdx.x;
   const bool tail = blockIdx.x == HT_NBLK;
@@ -288,14 +263,14 @@ __global__ __launch_bounds__(256) void head_adamw_kernel(HtAdam A, float* params
     v = *reinterpret_cast<const float4*>(exp_avg_sq + flat);
   }
   const float s = tid < HT_NBLK ? ws[W_PART + tid] : 0.f;
-  const float norm = sqrtf(ht_tree_sum(s, red, tid) + ws[W_PART + HT_NBLK]);
-  const float c = fminf(A.max_norm / (norm + 1e-6f), 1.0f);  // clip_grad_norm_: clamped at 1, always applied
+  const float norm = sqrtf(block_tree_sum(s, red, tid) + ws[W_PART + HT_NBLK]);
+  const float c = fminf(max_norm / (norm + 1e-6f), 1.0f);  // clip_grad_norm_: clamped at 1, always applied
   if (!tail) {
     g.x *= c; g.y *= c; g.z *= c; g.w *= c;
-    ht_adam1(A, g.x, p.x, m.x, v.x);
-    ht_adam1(A, g.y, p.y, m.y, v.y);
-    ht_adam1(A, g.z, p.z, m.z, v.z);
-    ht_adam1(A, g.w, p.w, m.w, v.w);
+    adamw_update(A, g.x, p.x, m.x, v.x);
+    adamw_update(A, g.y, p.y, m.y, v.y);
+    adamw_update(A, g.z, p.z, m.z, v.z);
+    adamw_update(A, g.w, p.w, m.w, v.w);
     *reinterpret_cast<float4*>(params + flat) = p;
     *reinterpret_cast<float4*>(exp_avg + flat) = m;
     *reinterpret_cast<float4*>(exp_avg_sq + flat) = v;
@@ -305,24 +280,13 @@ __global__ __launch_bounds__(256) void head_adamw_kernel(HtAdam A, float* params
   for (int i = HT_NW1 + tid; i < kHeadTrainParams; i += 256) {
     float ps = params[i], ms = exp_avg[i], vs = exp_avg_sq[i];
     const float gc = ws[W_G + i] * c;
-    ht_adam1(A, gc, ps, ms, vs);
+    adamw_update(A, gc, ps, ms, vs);
     params[i] = ps;
     exp_avg[i] = ms;
     exp_avg_sq[i] = vs;
     if (grad_out) grad_out[i] = gc;
   }
   if (tid == 0) *gnorm_out = norm;
-}
-
-// b^n by squaring, a function of (b, n) alone
-double ht_ipow(double b, int n) {
-  double r = 1.0;
-  while (n > 0) {
-    if (n & 1) r *= b;
-    b *= b;
-    n >>= 1;
-  }
-  return r;
 }
 
 }  // namespace
@@ -339,17 +303,13 @@ hipError_t launch_head_train_epoch(const float* feat, const int32_t* labels, int
   const float scale = (float)(1.0 / (1.0 - (double)p_drop));
   for (int st = 0; st < nsteps; ++st) {
     const int pos0 = st * batch, rows = std::min(batch, N - pos0);
-    const int step = step0 + st + 1;
-    const double lr = lr_steps[st];
-    const double bc1 = 1.0 - ht_ipow(beta1, step), bc2 = 1.0 - ht_ipow(beta2, step);
-    const HtAdam A{(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                   (float)eps, (float)(lr / bc1), (float)std::sqrt(bc2), (float)max_norm};
+    const AdamScalars A = adam_scalars(lr_steps[st], beta1, beta2, eps, weight_decay, step0 + st + 1);
     hipLaunchKernelGGL(head_pre_kernel, dim3(HT_H / PJ_J), dim3(256), 0, s, feat, N, perm, pos0, rows, params, ws);
     hipLaunchKernelGGL(head_mid_kernel, dim3(1), dim3(256), 0, s, labels, N, perm, pos0, rows, keep, scale, params, ws,
                        step_loss + st, step_correct + st, (float*)nullptr, 1);
     hipLaunchKernelGGL(head_wgrad_kernel, dim3(HT_NBLK), dim3(256), 0, s, rows, ws);
-    hipLaunchKernelGGL(head_adamw_kernel, dim3(HT_NBLK + 1), dim3(256), 0, s, A, params, exp_avg, exp_avg_sq, ws,
-                       step_gnorm + st, st == nsteps - 1 ? grad_out : nullptr);
+    hipLaunchKernelGGL(head_adamw_kernel, dim3(HT_NBLK + 1), dim3(256), 0, s, A, (float)max_norm, params,
+                       exp_avg, exp_avg_sq, ws, step_gnorm + st, st == nsteps - 1 ? grad_out : nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -66,6 +66,7 @@ class Engine:
             self._auto_set["effnet_fp32"] = self.get_option("effnet_fp32")
         self.clip_stream_check = None
         self.vault_n = 0
+        self._workspaces = {}
         if detector_state is not None:
             self.load_state(detector_state, "")
         if clip_state is not None:
@@ -567,14 +568,19 @@ class Engine:
 
     CLIP_TRAIN_PARAMS = 655361  # MMF_CLIP_TRAIN_PARAMS: visual [512][768] | text [512][512] | logit_scale
 
-    def _clip_train_ws(self, batch: int) -> torch.Tensor:
-        need = int(self.lib.mmf_clip_train_ws_bytes(int(batch)))
-        ws = getattr(self, "_ct_ws", None)
+    def _workspace(self, name: str, need: int) -> torch.Tensor:
+        """The device byte buffer kept under ``name``, grown to at least ``need`` bytes."""
+        ws = self._workspaces.get(name)
         if ws is None or ws.numel() < need:
-            ws = self._ct_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            ws = self._workspaces[name] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
         return ws
 
-    def _clip_train_check(self, what: str, tensors) -> None:
+    @staticmethod
+    def _nsteps(N: int, batch: int) -> int:
+        return max(1, -(-N // max(1, int(batch))))
+
+    def _check_tensors(self, what: str, tensors) -> None:
+        """tensors: (name, tensor, dtype, elements, optional) of a trainer or eval call's device arguments."""
         for name, t, dt, n, optional in tensors:
             if t is None and optional:
                 continue
@@ -590,14 +596,14 @@ class Engine:
         exp_avg_sq float32 [655361], updated in place.  Returns (step_loss, step_gnorm) float32 [nsteps] on
         the device; nothing is synchronised."""
         N, P = int(perm.shape[0]), self.CLIP_TRAIN_PARAMS
-        self._clip_train_check("clip_train_epoch", (
+        self._check_tensors("clip_train_epoch", (
             ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
             ("perm", perm, torch.int32, N, False), ("params", params, torch.float32, P, False),
             ("exp_avg", exp_avg, torch.float32, P, False), ("exp_avg_sq", exp_avg_sq, torch.float32, P, False),
             ("grad_out", grad_out, torch.float32, P, True)))
-        nsteps = max(1, -(-N // max(1, int(batch))))
+        nsteps = self._nsteps(N, batch)
         step_loss, step_gnorm = self._f32(nsteps), self._f32(nsteps)
-        ws = self._clip_train_ws(batch)
+        ws = self._workspace("clip_train", self.lib.mmf_clip_train_ws_bytes(int(batch)))
         check(self.lib.mmf_clip_train_epoch(ptr(img_feat), ptr(txt_feat), N, ptr(perm), int(batch), float(lr),
                                             float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                             float(max_norm), int(step0), ptr(params), ptr(exp_avg), ptr(exp_avg_sq),
@@ -609,25 +615,18 @@ class Engine:
         """validate's forward on cached features (mmf_clip_contrastive_eval): consecutive batches in row
         order -> (batch_loss float32 [nbatches], row_cos float32 [N]) on the device."""
         N = int(img_feat.shape[0])
-        self._clip_train_check("clip_contrastive_eval", (
+        self._check_tensors("clip_contrastive_eval", (
             ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
             ("params", params, torch.float32, self.CLIP_TRAIN_PARAMS, False)))
-        nb = max(1, -(-N // max(1, int(batch))))
+        nb = self._nsteps(N, batch)
         batch_loss, row_cos = self._f32(nb), self._f32(N)
-        ws = self._clip_train_ws(batch)
+        ws = self._workspace("clip_train", self.lib.mmf_clip_train_ws_bytes(int(batch)))
         check(self.lib.mmf_clip_contrastive_eval(ptr(img_feat), ptr(txt_feat), N, int(batch), ptr(params),
                                                  ptr(batch_loss), ptr(row_cos), ptr(ws), ws.numel(), stream_ptr()),
               "mmf_clip_contrastive_eval")
         return batch_loss, row_cos
 
     HEAD_PARAMS = 197378  # MMF_HEAD_PARAMS: 0.weight [256][768] | 0.bias [256] | 3.weight [2][256] | 3.bias [2]
-
-    def _head_train_ws(self, batch: int) -> torch.Tensor:
-        need = int(self.lib.mmf_head_train_ws_bytes(int(batch)))
-        ws = getattr(self, "_ht_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._ht_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-        return ws
 
     def head_train_epoch(self, feat, labels, perm, keep, p_drop: float, batch: int, lr_steps, betas, eps: float,
                          weight_decay: float, max_norm: float, step0: int, params, exp_avg, exp_avg_sq,
@@ -638,18 +637,18 @@ class Engine:
         updated in place.  Returns (step_loss float32, step_correct int32, step_gnorm float32) [nsteps] on the
         device; nothing is synchronised."""
         N, P = int(perm.shape[0]), self.HEAD_PARAMS
-        self._clip_train_check("head_train_epoch", (
+        self._check_tensors("head_train_epoch", (
             ("feat", feat, torch.float32, 768 * N, False), ("labels", labels, torch.int32, N, False),
             ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, 4 * N, True),
             ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
             ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
-        nsteps = max(1, -(-N // max(1, int(batch))))
+        nsteps = self._nsteps(N, batch)
         lrs = np.ascontiguousarray(np.asarray(lr_steps, dtype=np.float64).reshape(-1))
         if lrs.shape[0] != nsteps:
             raise ValueError(f"head_train_epoch: {lrs.shape[0]} learning rates for {nsteps} steps")
         step_loss, step_gnorm = self._f32(nsteps), self._f32(nsteps)
         step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
-        ws = self._head_train_ws(batch)
+        ws = self._workspace("head_train", self.lib.mmf_head_train_ws_bytes(int(batch)))
         check(self.lib.mmf_head_train_epoch(ptr(feat), ptr(labels), N, ptr(perm), ptr(keep), float(p_drop), int(batch),
                                             lrs.ctypes.data_as(ctypes.c_void_p), float(betas[0]), float(betas[1]),
                                             float(eps), float(weight_decay), float(max_norm), int(step0), ptr(params),
@@ -662,12 +661,12 @@ class Engine:
         """validate's forward on cached CLS rows (mmf_head_eval): consecutive batches in row order ->
         (batch_loss float32 [nbatches], row_logits float32 [N, 2]) on the device."""
         N = int(labels.shape[0])
-        self._clip_train_check("head_eval", (
+        self._check_tensors("head_eval", (
             ("feat", feat, torch.float32, 768 * N, False), ("labels", labels, torch.int32, N, False),
             ("params", params, torch.float32, self.HEAD_PARAMS, False)))
-        nb = max(1, -(-N // max(1, int(batch))))
+        nb = self._nsteps(N, batch)
         batch_loss, row_logits = self._f32(nb), self._f32(N, 2)
-        ws = self._head_train_ws(batch)
+        ws = self._workspace("head_train", self.lib.mmf_head_train_ws_bytes(int(batch)))
         check(self.lib.mmf_head_eval(ptr(feat), ptr(labels), N, int(batch), ptr(params), ptr(batch_loss),
                                      ptr(row_logits), ptr(ws), ws.numel(), stream_ptr()), "mmf_head_eval")
         return batch_loss, row_logits
@@ -681,12 +680,12 @@ class Engine:
         uint64 masks' bits) or None; params / exp_avg / exp_avg_sq float32 [2562], updated in place.  Returns
         (step_loss float32 [nsteps], step_correct int32 [nsteps]) on the device; nothing is synchronised."""
         R, N, P = int(labels.shape[0]), int(perm.shape[0]), self.EFFCLS_PARAMS
-        self._clip_train_check("effcls_train_epoch", (
+        self._check_tensors("effcls_train_epoch", (
             ("feat", feat, torch.float32, 1280 * R, False), ("labels", labels, torch.int32, R, False),
             ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, 20 * N, True),
             ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
             ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
-        nsteps = max(1, -(-N // max(1, int(batch))))
+        nsteps = self._nsteps(N, batch)
         step_loss = self._f32(nsteps)
         step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
         check(self.lib.mmf_effcls_train_epoch(ptr(feat), ptr(labels), R, ptr(perm), N, ptr(keep), float(p_drop),
@@ -700,10 +699,10 @@ class Engine:
         """validate's forward on cached pooled rows (mmf_effcls_eval): consecutive batches in row order ->
         (batch_loss float32 [nbatches], row_logits float32 [R, 2]) on the device."""
         R = int(labels.shape[0])
-        self._clip_train_check("effcls_eval", (
+        self._check_tensors("effcls_eval", (
             ("feat", feat, torch.float32, 1280 * R, False), ("labels", labels, torch.int32, R, False),
             ("params", params, torch.float32, self.EFFCLS_PARAMS, False)))
-        nb = max(1, -(-R // max(1, int(batch))))
+        nb = self._nsteps(R, batch)
         batch_loss, row_logits = self._f32(nb), self._f32(R, 2)
         check(self.lib.mmf_effcls_eval(ptr(feat), ptr(labels), R, int(batch), ptr(params), ptr(batch_loss),
                                        ptr(row_logits), stream_ptr()), "mmf_effcls_eval")
@@ -731,10 +730,7 @@ class Engine:
         if q.dim() != 2 or bank.dim() != 2 or q.shape[1] != bank.shape[1]:
             raise ValueError(f"q_unit {tuple(q.shape)} and bank {tuple(bank.shape)} must be [B, D] and [N, D]")
         B, N, D = q.shape[0], bank.shape[0], bank.shape[1]
-        need = int(self.lib.mmf_vault_search_ws_bytes(B, k, nblocks))
-        ws = getattr(self, "_search_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._search_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace("vault_search", self.lib.mmf_vault_search_ws_bytes(B, k, nblocks))
         sims, idx = self._f32(B, k), torch.empty((B, k), dtype=torch.int32, device=self.device)
         disc, tsim = self._f32(B), self._f32(B)
         if text_emb is not None:
@@ -765,20 +761,12 @@ class Engine:
         step_correct int32 [nsteps]) on the device; nothing is synchronised."""
         N = int(labels.shape[0])
         P = self.FUSION_PARAMS
-        for name, t, dt, n, optional in (("scores5", scores5, torch.float32, 5 * N, False),
-                                         ("labels", labels, torch.int32, N, False),
-                                         ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, N, True),
-                                         ("params", params, torch.float32, P, False),
-                                         ("exp_avg", exp_avg, torch.float32, P, False),
-                                         ("exp_avg_sq", exp_avg_sq, torch.float32, P, False),
-                                         ("grad_out", grad_out, torch.float32, P, True)):
-            if t is None and optional:
-                continue
-            if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.is_contiguous()
-                    and t.numel() == n):
-                raise ValueError(f"fusion_train_epoch: {name} must be a contiguous {dt} tensor of {n} elements on "
-                                 f"{self.device}")
-        nsteps = max(1, -(-N // max(1, int(batch))))
+        self._check_tensors("fusion_train_epoch", (
+            ("scores5", scores5, torch.float32, 5 * N, False), ("labels", labels, torch.int32, N, False),
+            ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, N, True),
+            ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
+            ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
+        nsteps = self._nsteps(N, batch)
         step_loss = self._f32(nsteps)
         step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
         check(self.lib.mmf_fusion_train_epoch(ptr(scores5), ptr(labels), N, ptr(perm), ptr(keep), float(p_drop),

@@ -21,7 +21,9 @@ import numpy as np
 import torch
 
 from . import io_utils
+from . import training_common as TC
 from . import weights as W
+from .training_common import pack_keep, split_like as _split  # pack_keep here: bool [N, 64] -> uint64 [N]
 
 P_DROP = 0.2  # fusion_layer's Dropout (misinfo_forensics.py:86)
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.AdamW defaults (train_fusion_judge.py:179-183)
@@ -115,12 +117,6 @@ def extract_scores(forensics, texts: Sequence[str], image_paths: Sequence[str]) 
 # ---------------------------------------------------------------------------------------------
 # the epoch plan
 # ---------------------------------------------------------------------------------------------
-def pack_keep(mask) -> np.ndarray:
-    """bool [N, 64] -> uint64 [N], bit j = mask[:, j]."""
-    m = np.asarray(mask, dtype=bool)
-    return np.bitwise_or.reduce(m.astype(np.uint64) << np.arange(64, dtype=np.uint64), axis=1)
-
-
 def plan(N: int, batch_size: int, epochs: int, lr: float, seed: int):
     """Per epoch (perm int32 [N], keep uint64 [N], lr): the DataLoader's shuffle as ``torch.randperm``, the
     Dropout(0.2) masks as ``torch.rand(N, 64) >= 0.2`` (row i = the row at position i of the epoch's
@@ -159,28 +155,11 @@ def flatten_fusion(fusion_layer) -> torch.Tensor:
     return torch.cat([sd[k].detach().reshape(-1).float() for k in PARAM_KEYS])
 
 
-def _split(flat: torch.Tensor, like) -> List[torch.Tensor]:
-    out, o = [], 0
-    for p in like:
-        out.append(flat[o:o + p.numel()].reshape(p.shape))
-        o += p.numel()
-    return out
-
-
 def optimizer_state_dict(fusion_layer, exp_avg, exp_avg_sq, steps: int, lr: float, initial_lr: float,
                          weight_decay: float) -> dict:
     """The state dict ``torch.optim.AdamW(fusion_layer.parameters())`` would hold with these moments and
     step count: built by a real AdamW, so it loads into one."""
-    prm = list(fusion_layer.parameters())
-    opt = torch.optim.AdamW(prm, lr=initial_lr, weight_decay=weight_decay)
-    for p, m, v in zip(prm, _split(exp_avg, prm), _split(exp_avg_sq, prm)):
-        opt.state[p] = {"step": torch.tensor(float(steps)), "exp_avg": m.detach().clone().to(p.device),
-                        "exp_avg_sq": v.detach().clone().to(p.device)}
-    sd = opt.state_dict()
-    for gr in sd["param_groups"]:
-        gr["lr"] = lr
-        gr["initial_lr"] = initial_lr  # the key CosineAnnealingLR adds to the groups it schedules
-    return sd
+    return TC.adamw_state_dict(fusion_layer.parameters(), exp_avg, exp_avg_sq, steps, lr, initial_lr, weight_decay)
 
 
 class FusionTrainer:
@@ -196,17 +175,10 @@ class FusionTrainer:
     def fit(self, scores, labels, checkpoint_path: Optional[str] = None) -> List[dict]:
         f = self.forensics
         eng, det = f.engine, f.detector
-        scores = np.ascontiguousarray(np.asarray(scores, dtype=np.float32))
-        labels = np.asarray(labels)
-        if scores.ndim != 2 or scores.shape[1] != 5 or labels.shape != (scores.shape[0],) or len(labels) == 0:
-            raise ValueError(f"scores {scores.shape} must be [N, 5] and labels {labels.shape} [N], N >= 1")
-        if not np.isfinite(scores).all():
-            raise ValueError("scores must be finite")
-        if not np.isin(labels, (0, 1)).all():
-            raise ValueError("labels must be 0 or 1")
+        scores, labels = TC.check_rows("training", (scores,), (5,), labels, noun="scores")
         N, dev = len(labels), eng.device
         x = torch.from_numpy(scores).to(dev)
-        y = torch.from_numpy(labels.astype(np.int32)).to(dev)
+        y = torch.from_numpy(labels).to(dev)
         params = flatten_fusion(det.fusion_layer).to(dev).contiguous()
         m, v = torch.zeros_like(params), torch.zeros_like(params)
         steps_per_epoch = -(-N // self.batch_size)

@@ -30,7 +30,9 @@ import numpy as np
 import torch
 
 from . import io_utils
+from . import training_common as TC
 from . import weights as W
+from .training_common import pack_keep, split_like as _split  # pack_keep here: bool [N, 256] -> uint64 [N, 4]
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.AdamW defaults (train_ai_head.py:433-437)
 P_DROP = 0.3                     # the heads' Dropout (misinfo_forensics.py:60, 67)
@@ -99,12 +101,6 @@ def split_indices(N: int, val_fraction: float = 0.2, seed: int = 42) -> Tuple[np
     return perm[:N - n_val].astype(np.int64), perm[N - n_val:].astype(np.int64)
 
 
-def pack_keep(mask: np.ndarray) -> np.ndarray:
-    """bool [N, 256] -> uint64 [N, 4]: word w bit j = hidden unit 64 w + j kept."""
-    m = np.asarray(mask, dtype=bool).reshape(-1, 4, 64).astype(np.uint64)
-    return (m << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
-
-
 def _scheduler(total_steps: int, lr: float, warmup_ratio: float):
     from transformers import get_cosine_schedule_with_warmup
     opt = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr)
@@ -155,28 +151,12 @@ def flatten_head(head) -> torch.Tensor:
     return flat
 
 
-def _split(flat: torch.Tensor, like) -> List[torch.Tensor]:
-    out, o = [], 0
-    for p in like:
-        out.append(flat[o:o + p.numel()].reshape(p.shape))
-        o += p.numel()
-    return out
-
-
 def optimizer_state_dict(head, exp_avg, exp_avg_sq, steps: int, lr: float, initial_lr: float,
                          weight_decay: float) -> dict:
     """The state dict the reference's ``AdamW(filter(requires_grad, model.parameters()))`` would hold with these
     moments and step count: built by a real AdamW over the head's ``parameters()``, so it loads into one."""
-    prm = list(head.parameters())
-    opt = torch.optim.AdamW(prm, lr=initial_lr, weight_decay=weight_decay)
-    for p, m, v in zip(prm, _split(exp_avg, prm), _split(exp_avg_sq, prm)):
-        opt.state[p] = {"step": torch.tensor(float(steps)), "exp_avg": m.detach().clone().cpu(),
-                        "exp_avg_sq": v.detach().clone().cpu()}
-    sd = opt.state_dict()
-    for gr in sd["param_groups"]:
-        gr["lr"] = lr
-        gr["initial_lr"] = initial_lr  # the key LambdaLR adds to the groups it schedules
-    return sd
+    return TC.adamw_state_dict(head.parameters(), exp_avg, exp_avg_sq, steps, lr, initial_lr, weight_decay,
+                               device="cpu")
 
 
 class HeadTrainer:
@@ -196,15 +176,7 @@ class HeadTrainer:
 
     @staticmethod
     def _data(feats, labels, what):
-        x = np.ascontiguousarray(np.asarray(feats, dtype=np.float32))
-        y = np.asarray(labels)
-        if x.ndim != 2 or x.shape[1] != WIDTH or len(x) == 0 or y.shape != (x.shape[0],):
-            raise ValueError(f"{what} features {x.shape} / labels {y.shape} must be [N, 768] / [N], N >= 1")
-        if not np.isfinite(x).all():
-            raise ValueError(f"{what} features must be finite")
-        if not np.isin(y, (0, 1)).all():
-            raise ValueError(f"{what} labels must be 0 or 1")
-        return x, y.astype(np.int32)
+        return TC.check_rows(what, (feats,), (WIDTH,), labels)
 
     def fit(self, train_feats, train_labels, val_feats, val_labels, checkpoint_path: Optional[str] = None,
             save_full_model: bool = True) -> List[dict]:
@@ -227,14 +199,8 @@ class HeadTrainer:
                                              EPS, self.weight_decay, self.max_norm, step0, params, m, v)
             bl, lg = eng.head_eval(xv, yv_d, bs, params)
             step0 += spe
-            train_loss = float(sl.cpu().numpy().astype(np.float64).mean())  # total_loss / len(dataloader) (:255)
-            train_acc = float(100 * int(sc.cpu().numpy().astype(np.int64).sum()) / N)
-            val_loss = float(bl.cpu().numpy().astype(np.float64).mean())    # :294
-            if not (np.isfinite(train_loss) and np.isfinite(val_loss)):
-                raise FloatingPointError(f"epoch {epoch}: the loss is not finite")
-            lg = lg.cpu().numpy()
-            pred = (lg[:, 1] > lg[:, 0]).astype(np.int64)  # torch.argmax: a tie is class 0
-            val_acc = float(100 * int((pred == yv).sum()) / len(yv))
+            # train_ai_head.py:255, :294
+            train_loss, train_acc, val_loss, val_acc, pred = TC.classifier_epoch_metrics(epoch, sl, sc, bl, lg, N, yv)
             history.append({"epoch": epoch, "train_loss": train_loss, "train_acc": train_acc, "val_loss": val_loss,
                             "val_acc": val_acc, "lr": float(lrs[-1])})
             if val_loss < best_loss:  # :491

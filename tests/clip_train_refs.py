@@ -39,7 +39,8 @@ import functools
 
 import numpy as np
 
-U = 2.0 ** -24
+from tests.train_refs_common import U, adam, chain_err, clip_coef, flat  # noqa: F401
+
 D, KV, KT = 512, 768, 512
 NV, NT = D * KV, D * KT
 N_PARAMS = NV + NT + 1
@@ -131,28 +132,9 @@ def forward_backward(pi, pt, Wv, Wt, ls, dtype):
     return r
 
 
-def flat(grads):
-    return np.concatenate([g.reshape(-1) for g in grads])
-
-
-def clip_coef(norm, max_norm, dtype):
-    dt = dtype
-    return min(dt(max_norm) / (dt(norm) + dt(1e-6)), dt(1.0))
-
-
 def adamw(p, m, v, g, lr, step, dtype, betas=BETAS, eps=EPS, wd=WD):
-    """torch.optim.AdamW's single-tensor update on flat arrays, in place; the scalars in double, rounded to
-    dtype once."""
-    dt = dtype
-    b1, b2 = betas
-    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-    decay, w1, fb2, w2 = dt(1.0 - lr * wd), dt(1.0 - b1), dt(b2), dt(1.0 - b2)
-    step_size, bc2s, feps = dt(lr / bc1), dt(np.sqrt(bc2)), dt(eps)
-    p *= decay
-    m += w1 * (g - m)
-    v *= fb2
-    v += w2 * (g * g)
-    p -= step_size * (m / (np.sqrt(v) / bc2s + feps))
+    """torch.optim.AdamW's single-tensor update on flat arrays, in place."""
+    adam(p, m, v, g, lr, step, dtype, wd, "decoupled", betas, eps)
 
 
 def epoch(img, txt, perm, batch, lr, step0, params, exp_avg, exp_avg_sq, dtype=np.float64, wd=WD,
@@ -212,13 +194,6 @@ def lower_median_accuracy(cos, labels):
     cos, labels = np.asarray(cos), np.asarray(labels)
     thr = np.sort(cos)[(len(cos) - 1) // 2]
     return float(((cos <= thr).astype(np.int64) == labels).mean())
-
-
-def chain_err(x, w):
-    """First-order rounding error of the ascending-index fmaf chains x[i] . w[j] (the kernel's contract fixes the
-    order): every step rounds its partial sum once, so the error is at most U sum_k |partial sum k|, from the
-    float64 partial sums.  x [M, K], w [N, K] -> [M, N]."""
-    return U * np.stack([np.abs(np.cumsum(w * xi, axis=1)).sum(1) for xi in x])
 
 
 def step_bounds(pi, pt, params64, max_norm=MAX_NORM):

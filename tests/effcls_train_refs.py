@@ -23,7 +23,7 @@ The multi-step floor.  An Adam step rounds a parameter once (p - update), by at 
 default initialisation the classifier's parameters start below 1 / 32 and stay below 1 / 16 (half-ulp 2^-29), so two
 correct fp32 evaluations may part by FLOOR = 2 x 2^-29 per step.
 
-Conditioning of a multi-step case: head_train_refs.Drift (float64 run only), fed with this model's gradient
+Conditioning of a multi-step case: train_refs_common.Drift (float64 run only), fed with this model's gradient
 magnitudes (``_magnitudes``): the bound is K <= 8 x max(e32, FLOOR x steps, cond), and what keeps it from hiding a
 failure is asserted on the reference alone (tests/test_effcls_train_refs_cpu.py): it stays below 0.1 x
 max |p64_final - p_initial|, so a kernel that trains differently (a missing dropout scale, AdamW's decoupled decay in
@@ -33,9 +33,9 @@ import functools
 
 import numpy as np
 
-from tests.head_train_refs import Drift
+from tests import train_refs_common as C
+from tests.train_refs_common import Drift, U, flat, pack_keep  # noqa: F401
 
-U = 2.0 ** -24
 K = 1280
 WORDS = K // 64
 N_PARAMS = 2 * K + 2  # MMF_EFFCLS_PARAMS
@@ -85,15 +85,7 @@ def draws(N: int, seed: int = 0):
     return a.copy(), b.copy()
 
 
-def pack_keep(mask) -> np.ndarray:
-    """bool [N, 1280] -> uint64 [N, 20]: word w bit j = input channel 64 w + j."""
-    m = np.asarray(mask, bool).reshape(-1, WORDS, 64).astype(np.uint64)
-    return (m << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
-
-
-def unpack_keep(keep) -> np.ndarray:
-    k = np.asarray(keep, np.uint64).reshape(-1, WORDS, 1)
-    return ((k >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(-1, K)
+unpack_keep = functools.partial(C.unpack_keep, width=K)  # uint64 [N, 20] -> bool [N, 1280]; pack_keep is its inverse
 
 
 def _mult(keep, pos, dtype):
@@ -129,27 +121,10 @@ def forward_backward(x, mult, W, b, y, dtype):
     return r
 
 
-def flat(grads):
-    return np.concatenate([g.reshape(-1) for g in grads])
-
-
 def adam(p, m, v, g, lr, step, dtype, wd=0.0, betas=BETAS, eps=EPS, decoupled=False):
-    """torch.optim.Adam's single-tensor update on flat arrays, in place; the scalars in double, rounded to dtype
-    once.  decoupled: AdamW's p *= 1 - lr wd instead of g += wd p (the broken restatement of the CPU test)."""
-    dt = dtype
-    b1, b2 = betas
-    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-    w1, fb2, w2 = dt(1.0 - b1), dt(b2), dt(1.0 - b2)
-    step_size, bc2s, feps = dt(lr / bc1), dt(np.sqrt(bc2)), dt(eps)
-    if wd != 0:
-        if decoupled:
-            p *= dt(1.0 - lr * wd)
-        else:
-            g = g + dt(wd) * p
-    m += w1 * (g - m)
-    v *= fb2
-    v += w2 * (g * g)
-    p -= step_size * (m / (np.sqrt(v) / bc2s + feps))
+    """torch.optim.Adam's single-tensor update on flat arrays, in place.  decoupled: AdamW's p *= 1 - lr wd instead
+    of g += wd p (the broken restatement of the CPU test)."""
+    C.adam(p, m, v, g, lr, step, dtype, wd, "decoupled" if decoupled else "l2", betas, eps)
 
 
 def _magnitudes(r, dropout):

@@ -31,7 +31,9 @@ import functools
 
 import numpy as np
 
-U = 2.0 ** -24
+from tests import train_refs_common as C
+from tests.train_refs_common import U, flat, pack_keep  # noqa: F401
+
 SHAPES = ((64, 5), (64,), (32, 64), (32,), (2, 32), (2,))  # fusion_layer.{0,3,5}.{weight,bias}
 KEYS = ("0.weight", "0.bias", "3.weight", "3.bias", "5.weight", "5.bias")
 N_PARAMS = sum(int(np.prod(s)) for s in SHAPES)
@@ -82,13 +84,7 @@ def masks(N: int, seed: int = SEED) -> np.ndarray:
     return np.random.default_rng([seed, N, 64]).uniform(size=(N, 64)) >= P_DROP
 
 
-def pack_keep(mask) -> np.ndarray:
-    m = np.asarray(mask, dtype=bool)
-    return np.bitwise_or.reduce(m.astype(np.uint64) << np.arange(64, dtype=np.uint64), axis=1)
-
-
-def unpack_keep(keep) -> np.ndarray:
-    return ((np.asarray(keep, np.uint64)[:, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+unpack_keep = functools.partial(C.unpack_keep, width=64)  # uint64 [N] -> bool [N, 64]; pack_keep is its inverse
 
 
 def forward_backward(x, y, keep_mask, p_drop, P, dtype):
@@ -124,17 +120,8 @@ def forward_backward(x, y, keep_mask, p_drop, P, dtype):
 
 def adamw(P, M, V, G, lr, step, dtype, betas=BETAS, eps=EPS, wd=WD):
     """torch.optim.AdamW's single-tensor update, in place; the scalars in double, rounded to dtype once."""
-    dt = dtype
-    b1, b2 = betas
-    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-    decay, w1, fb2, w2 = dt(1.0 - lr * wd), dt(1.0 - b1), dt(b2), dt(1.0 - b2)
-    step_size, bc2s, feps = dt(lr / bc1), dt(np.sqrt(bc2)), dt(eps)
     for p, m, v, g in zip(P, M, V, G):
-        p *= decay
-        m += w1 * (g - m)
-        v *= fb2
-        v += w2 * (g * g)
-        p -= step_size * (m / (np.sqrt(v) / bc2s + feps))
+        C.adam(p, m, v, g, lr, step, dtype, wd, "decoupled", betas, eps)
 
 
 def epoch(scores, labels, perm, keep, p_drop, batch, lr, step0, params, exp_avg, exp_avg_sq, dtype=np.float64,
@@ -158,7 +145,7 @@ def epoch(scores, labels, perm, keep, p_drop, batch, lr, step0, params, exp_avg,
             cond = max(cond, _conditioning(r, scores[src], P, V, lr, step0 + s + 1))
         losses.append(float(r["loss"]))
         corrects.append(r["correct"])
-    return np.array(losses), np.array(corrects), np.concatenate([a.reshape(-1) for a in g]), margin, cond
+    return np.array(losses), np.array(corrects), flat(g), margin, cond
 
 
 def _conditioning(r, x, P, V, lr, step):
@@ -217,8 +204,7 @@ def step_bounds(x, y, keep_mask, p_drop, params64):
         return e_d.sum(0) + U * (rows + 1) * d.sum(0)
     tol = [wgrad(adz1, e_dz1, ax, np.zeros_like(ax)), bgrad(adz1, e_dz1), wgrad(adz2, e_dz2, a1, e_a1),
            bgrad(adz2, e_dz2), wgrad(adl, e_dl, h2, e_z2), bgrad(adl, e_dl)]
-    return dict(r=r, grad=np.concatenate([g.reshape(-1) for g in r["grads"]]),
-                grad_tol=2 * np.concatenate([t.reshape(-1) for t in tol]), loss_tol=float(loss_tol),
+    return dict(r=r, grad=flat(r["grads"]), grad_tol=2 * flat(tol), loss_tol=float(loss_tol),
                 margin_tol=2 * e_margin)
 
 

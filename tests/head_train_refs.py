@@ -27,7 +27,7 @@ Conditioning of a multi-step case (``Drift``, float64 run only).  Adam divides a
 magnitude, and its first steps are sign-like: a gradient that is tiny against the terms of its own sum can come
 out with either sign.  Any fp32 evaluation of a gradient sum_r a_r b_r carries at least half an ulp of every term,
 and another half for each operand that is itself a rounded value, however small the result (``_magnitudes``).
-``Drift`` carries that error through AdamW's update to first order, step by step; cond = the largest distance over
+``Drift`` (tests/train_refs_common.py) carries that error through AdamW's update to first order, step by step; cond = the largest distance over
 the parameters at which two correct fp32 evaluations can end.  Among 196,608 weights some gradient is always tiny
 against its own terms, so at the reference's lr = 1e-3 cond lies far above FLOOR x steps and is part of the bound:
 K <= 8 x max(e32, FLOOR x steps, cond).  What keeps that bound from hiding a failure is asserted on the reference
@@ -38,7 +38,9 @@ import functools
 
 import numpy as np
 
-U = 2.0 ** -24
+from tests.train_refs_common import Drift, U, adam, chain_err, clip_coef, flat, pack_keep  # noqa: F401
+from tests.train_refs_common import unpack_keep as _unpack_keep
+
 K, H = 768, 256
 NW1 = H * K
 O_B1, O_W2, O_B2 = NW1, NW1 + H, NW1 + H + 2 * H
@@ -95,15 +97,7 @@ def draws(N: int, seed: int = 0, gain: float = 1.0):
     return a.copy(), b.copy()
 
 
-def pack_keep(mask) -> np.ndarray:
-    """bool [N, 256] -> uint64 [N, 4]: word w bit j = hidden unit 64 w + j."""
-    m = np.asarray(mask, bool).reshape(-1, 4, 64).astype(np.uint64)
-    return (m << np.arange(64, dtype=np.uint64)).sum(-1, dtype=np.uint64)
-
-
-def unpack_keep(keep) -> np.ndarray:
-    k = np.asarray(keep, np.uint64).reshape(-1, 4, 1)
-    return ((k >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(-1, 4 * 64)
+unpack_keep = functools.partial(_unpack_keep, width=H)  # uint64 [N, 4] -> bool [N, 256]; pack_keep is its inverse
 
 
 def lr_schedule(total_steps: int, lr: float, warmup_ratio: float = 0.1) -> np.ndarray:
@@ -153,28 +147,9 @@ def forward_backward(x, mult, W1, b1, W2, b2, y, dtype):
     return r
 
 
-def flat(grads):
-    return np.concatenate([g.reshape(-1) for g in grads])
-
-
-def clip_coef(norm, max_norm, dtype):
-    dt = dtype
-    return min(dt(max_norm) / (dt(norm) + dt(1e-6)), dt(1.0))
-
-
 def adamw(p, m, v, g, lr, step, dtype, betas=BETAS, eps=EPS, wd=WD):
-    """torch.optim.AdamW's single-tensor update on flat arrays, in place; the scalars in double, rounded to
-    dtype once."""
-    dt = dtype
-    b1, b2 = betas
-    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-    decay, w1, fb2, w2 = dt(1.0 - lr * wd), dt(1.0 - b1), dt(b2), dt(1.0 - b2)
-    step_size, bc2s, feps = dt(lr / bc1), dt(np.sqrt(bc2)), dt(eps)
-    p *= decay
-    m += w1 * (g - m)
-    v *= fb2
-    v += w2 * (g * g)
-    p -= step_size * (m / (np.sqrt(v) / bc2s + feps))
+    """torch.optim.AdamW's single-tensor update on flat arrays, in place."""
+    adam(p, m, v, g, lr, step, dtype, wd, "decoupled", betas, eps)
 
 
 def _mult(keep, pos, dtype):
@@ -221,41 +196,6 @@ def _magnitudes(r, W2):
                            2 * adl.sum(0)])
 
 
-class Drift:
-    """The conditioning number of a float64 run, accumulated over its steps.  AdamW is elementwise: the update of
-    step t is u_t = lr_t m_hat / (sqrt(v_hat) + eps), m and v the running means of the gradients g_s, s <= t, so
-        du_t / dg_s = lr_t [ (1 - b1) b1^(t-s) / bc1 / D  -  (m / bc1) (1 - b2) b2^(t-s) g_s / (bc2 sqrt(v_hat) D^2) ],
-    D = sqrt(v_hat) + eps.  (At step 1 the two terms cancel to lr eps / (|g| + eps)^2: the update is the gradient's
-    sign.)  A gradient error dg_s therefore moves the parameter after T steps by sum_t |du_t / dg_s| dg_s, each
-    step's part capped at 2 lr_t, the distance between the two signs.  cond = the largest such sum over the
-    parameters, with dg_s = coef_s U x (the magnitude of _magnitudes).  The feedback of a moved parameter into
-    later gradients is second order at these distances and left out."""
-
-    def __init__(self):
-        self.g, self.dg, self.total = [], [], None
-
-    def gradient(self, g, dg):
-        self.g.append(g.copy())
-        self.dg.append(dg)
-
-    def update(self, m, v, lr, step):
-        b1, b2 = BETAS
-        bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-        rv = np.sqrt(v / bc2)
-        D = rv + EPS
-        t = len(self.g) - 1
-        part = np.zeros_like(m)
-        for s, (g, dg) in enumerate(zip(self.g, self.dg)):
-            d = (1.0 - b1) * b1 ** (t - s) / bc1 / D - (m / bc1) * (1.0 - b2) * b2 ** (t - s) * g / (bc2 * np.maximum(rv, 1e-300) * D * D)
-            part += np.abs(d) * dg
-        part = np.minimum(lr * part, 2.0 * lr)
-        self.total = part if self.total is None else self.total + part
-
-    @property
-    def cond(self):
-        return float(self.total.max()) if self.total is not None else 0.0
-
-
 def evaluate(feat, labels, batch, params, dtype=np.float64):
     """validate's forward: no dropout, consecutive batches in row order -> (batch_loss [nb], row_logits [N, 2])."""
     N = feat.shape[0]
@@ -267,13 +207,6 @@ def evaluate(feat, labels, batch, params, dtype=np.float64):
         losses.append(float(r["loss"]))
         lg.append(r["lg"])
     return np.array(losses), np.concatenate(lg)
-
-
-def chain_err(x, w):
-    """First-order rounding error of the ascending-index fmaf chains x[i] . w[j] (the kernel's contract fixes the
-    order): every step rounds its partial sum once, so the error is at most U sum_k |partial sum k|, from the
-    float64 partial sums.  x [M, K], w [N, K] -> [M, N]."""
-    return U * np.stack([np.abs(np.cumsum(w * xi, axis=1)).sum(1) for xi in x])
 
 
 def forward_bounds(r, W2):
