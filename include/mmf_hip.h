@@ -32,7 +32,7 @@ extern "C" {
 #define MMF_ENOMEM (-12)
 #define MMF_EIO (-5)
 #define MMF_ERANGE (-34) /* an input outside a kernel's supported range (mmf_resize_pil: too many taps) */
-#define MMF_EUNSUPPORTED (-95) /* a valid input of a kind this path does not handle (mmf_jpeg_*: CMYK, lossless, ...) */
+#define MMF_EUNSUPPORTED (-95) /* a valid input of a kind this path does not handle (mmf_jpeg_*: CMYK, lossless, coefficients outside the exact range, ...) */
 
 #define MMF_DTYPE_F32 0
 #define MMF_DTYPE_I64 1
@@ -265,6 +265,18 @@ int mmf_resize_pil(mmf_handle* h, const uint8_t* src, const int64_t* offsets, co
  * extended sequential Huffman JPEGs with one scan, and progressive Huffman JPEGs (any scan script;
  * quantisation tables fixed before the first scan), grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0;
  * anything else returns MMF_EUNSUPPORTED (decode that file on the host).
+ *
+ * The exact range.  "Bit-exact with Pillow" holds while the integer IDCT stays where libjpeg's C code
+ * (64-bit, range limit by table[v & 1023]), libjpeg-turbo's SIMD code (16-bit lanes, a saturating
+ * clamp) and the device kernel (32-bit, the table's arithmetic) agree: for every block of the file
+ * |coef * q| <= 32767, |pass-1 workspace| <= 32767 and -512 <= pass-2 output <= 511 (the table wraps
+ * beyond: 512 -> 0).  Files an encoder writes are far inside; a file whose quantisation tables were
+ * rewritten (8-bit or 16-bit, Pq = 1) need not be.  The header cannot tell, so mmf_jpeg_header
+ * accepts such a file and the entropy decoders -- mmf_jpeg_entropy, mmf_jpeg_entropy_packed,
+ * mmf_jpeg_stage_packed and the batch form's rcs[k] -- return MMF_EUNSUPPORTED for a file with any
+ * block outside (outputs then hold no usable data, no staging room is reserved): decode that file on
+ * the host.  mmf_jpeg_reconstruct itself does not check: its operands must come from those decoders
+ * (or satisfy the same conditions).
  *
  * mmf_jpeg_header: host-only, no handle.  info[MMF_JPEG_INFO_LEN] = {width, height, ncomp, hmax, vmax,
  * bw0, bh0, bw1, bh1, bw2, bh2, blocks, 0...} (bw_c x bh_c = component c's MCU-padded block grid;

@@ -58,7 +58,9 @@ MMF_DEV void idct_1d(const int* d, int* o, int shift) {
   o[4] = (tmp13 - t0 + r) >> shift;
 }
 
-// jdmaster.c post-IDCT range limit: idct_range_limit[v & 1023] (CENTERJSAMPLE folded in)
+// jdmaster.c post-IDCT range limit: idct_range_limit[v & 1023] (CENTERJSAMPLE folded in).  A clamp for
+// -512 <= v <= 511 only (512 wraps to 0, where libjpeg-turbo's SIMD IDCT saturates): the host declines
+// files with a block outside that range (jpeg_host.cpp block_in_range), so none reaches this kernel.
 MMF_DEV uint32_t range_limit_idct(int v) {
   const int m = v & 1023;
   return (uint32_t)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);

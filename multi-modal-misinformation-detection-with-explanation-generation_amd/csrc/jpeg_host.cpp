@@ -8,7 +8,9 @@
 // Supported (mmf_jpeg_header returns 0): 8-bit baseline / extended sequential Huffman (SOF0/SOF1)
 // with one scan holding every component, or progressive Huffman (SOF2, any scan script; jdphuff.c), 1 component or 3 YCbCr components with luma sampling h, v <= 2
 // and chroma 1x1 (4:4:4, 4:2:2, 4:2:0); anything else returns MMF_EUNSUPPORTED and the caller decodes
-// that file on the host (Pillow).
+// that file on the host (Pillow).  A supported header is not yet a supported file: the entropy
+// decoders return MMF_EUNSUPPORTED when a block's dequantised coefficients leave the range in which
+// the device IDCT equals Pillow's (block_in_range below; rewritten quantisation tables).
 //
 // Coefficient layout (mmf_jpeg_entropy): component c's blocks as [bh_c][bw_c][64] int16, natural
 // (row-major) order, c = 0, 1, 2 back to back; bw_c = mcux * h_c, bh_c = mcuy * v_c (the MCU-padded
@@ -113,6 +115,7 @@ struct Jpeg {
   Comp comp[4];
   int nscan = 0, scomp[4] = {0, 0, 0, 0};
   uint16_t qt[4][64];
+  uint16_t qz[4][64];  // the same tables in zigzag order (as the file carries them)
   bool qt_present[4] = {false, false, false, false};
   Huff dc[4], ac[4];
   const uint8_t* scan = nullptr;  // entropy-coded segment start (progressive: the first SOS marker)
@@ -167,6 +170,7 @@ int parse(const uint8_t* d, int64_t n, Jpeg& j) {
         for (int i = 0; i < 64; ++i) {
           const int v = pq ? ((s[q + 2 * i] << 8) | s[q + 2 * i + 1]) : s[q + i];
           j.qt[tq][kZigzag[i]] = (uint16_t)v;
+          j.qz[tq][i] = (uint16_t)v;
         }
         q += pq ? 128 : 64;
         j.qt_present[tq] = true;
@@ -371,6 +375,93 @@ inline void decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int
   }
 }
 
+// ---- the exact range (oracle/jpeg_decode.py in_exact_range states the same predicate).  The device
+// IDCT is jidctint.c's in 32-bit arithmetic with table[v & 1023] as its range limit; Pillow's
+// libjpeg-turbo runs a SIMD islow IDCT (16-bit lanes, a saturating clamp).  They agree while, for
+// every block, |coef * q| <= 32767, |pass-1 workspace| <= 32767 and -512 <= pass-2 output <= 511
+// (the table lookup wraps past that: v = 512 gives 0).  Files an encoder writes stay far inside; a
+// file whose quantisation tables were rewritten need not, and is declined (MMF_EUNSUPPORTED: Pillow
+// decodes it).
+
+// Sum of |coef * q| at or below which a block is inside without running the IDCT: every basis value of
+// the 2-D IDCT is at most 1/4 in magnitude (C(u) C(v) cos cos / 4), so |v| <= sum / 4 = 509 before the
+// fixed-point rounding (well under 2), and pass 1 (a 1-D gain below 6 with PASS1_BITS) stays near 12k.
+constexpr int64_t kRangePrefilter = 2036;
+
+// jidctint.c's 1-D pass in 64-bit arithmetic (the oracle's integers)
+inline void islow_1d(const int64_t* d, int stride, int64_t* o, int ostride, int shift) {
+  const int64_t z2 = d[2 * stride], z3 = d[6 * stride];
+  int64_t z1 = (z2 + z3) * 4433;
+  const int64_t tmp2 = z1 + z3 * -15137, tmp3 = z1 + z2 * 6270;
+  const int64_t tmp0 = (d[0] + d[4 * stride]) * 8192, tmp1 = (d[0] - d[4 * stride]) * 8192;
+  const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  int64_t t0 = d[7 * stride], t1 = d[5 * stride], t2 = d[3 * stride], t3 = d[stride];
+  z1 = t0 + t3;
+  int64_t y2 = t1 + t2, y3 = t0 + t2, y4 = t1 + t3;
+  const int64_t z5 = (y3 + y4) * 9633;
+  t0 *= 2446;
+  t1 *= 16819;
+  t2 *= 25172;
+  t3 *= 12299;
+  z1 *= -7373;
+  y2 *= -20995;
+  y3 = y3 * -16069 + z5;
+  y4 = y4 * -3196 + z5;
+  t0 += z1 + y3;
+  t1 += y2 + y4;
+  t2 += y2 + y3;
+  t3 += z1 + y4;
+  const int64_t r = (int64_t)1 << (shift - 1);
+  o[0] = (tmp10 + t3 + r) >> shift;
+  o[7 * ostride] = (tmp10 - t3 + r) >> shift;
+  o[ostride] = (tmp11 + t2 + r) >> shift;
+  o[6 * ostride] = (tmp11 - t2 + r) >> shift;
+  o[2 * ostride] = (tmp12 + t1 + r) >> shift;
+  o[5 * ostride] = (tmp12 - t1 + r) >> shift;
+  o[3 * ostride] = (tmp13 + t0 + r) >> shift;
+  o[4 * ostride] = (tmp13 - t0 + r) >> shift;
+}
+
+// the three conditions on one dequantised block d[64] (natural order)
+bool block_in_range(const int64_t* d) {
+  for (int i = 0; i < 64; ++i)
+    if (d[i] > 32767 || d[i] < -32767) return false;
+  int64_t ws[64], o[8];
+  for (int u = 0; u < 8; ++u) islow_1d(d + u, 8, ws + u, 8, 11);  // columns
+  for (int i = 0; i < 64; ++i)
+    if (ws[i] > 32767 || ws[i] < -32767) return false;
+  for (int r = 0; r < 8; ++r) {  // rows
+    islow_1d(ws + r * 8, 1, o, 1, 18);
+    for (int i = 0; i < 8; ++i)
+      if (o[i] > 511 || o[i] < -512) return false;
+  }
+  return true;
+}
+
+// a dense natural-order block of quantised coefficients against its table
+bool dense_block_in_range(const int16_t* blk, const uint16_t* q) {
+  int64_t d[64], sum = 0;
+  for (int i = 0; i < 64; ++i) {
+    d[i] = (int64_t)blk[i] * q[i];
+    sum += d[i] < 0 ? -d[i] : d[i];
+  }
+  return sum <= kRangePrefilter || block_in_range(d);
+}
+
+// a packed record (mask + zigzag-order values) against its table
+bool record_in_range(const uint8_t* rec, const uint16_t* q) {
+  uint64_t mask;
+  memcpy(&mask, rec, 8);
+  const int16_t* val = reinterpret_cast<const int16_t*>(rec + 8);
+  int64_t d[64] = {};
+  int n = 0;
+  for (uint64_t m = mask; m; m &= m - 1) {
+    const int nat = kZigzag[__builtin_ctzll(m)];
+    d[nat] = (int64_t)val[n++] * q[nat];
+  }
+  return block_in_range(d);
+}
+
 }  // namespace
 
 extern "C" int mmf_jpeg_header(const uint8_t* data, int64_t nbytes, int32_t* info) {
@@ -397,8 +488,8 @@ extern "C" int mmf_jpeg_header(const uint8_t* data, int64_t nbytes, int32_t* inf
 
 namespace {
 
-// Entropy decoding of every block of the scan(s); on_block(global block index, dc, ac, pred) decodes
-// one block into the caller's representation, on_skip(global block index) marks a block of the
+// Entropy decoding of every block of the scan(s); on_block(global block index, component, dc, ac, pred)
+// decodes one block into the caller's representation, on_skip(global block index) marks a block of the
 // MCU-padded grid that no scan codes (non-interleaved scans cover only the component's extent).
 template <class OnBlock, class OnSkip>
 int walk_blocks(Jpeg& j, OnBlock&& on_block, OnSkip&& on_skip) {
@@ -427,7 +518,7 @@ int walk_blocks(Jpeg& j, OnBlock&& on_block, OnSkip&& on_skip) {
           b.restart();
           pred[0] = 0;
         }
-        on_block(b, (int64_t)by * bw[0] + bx, j.dc[c.td], j.ac[c.ta], pred[0]);
+        on_block(b, (int64_t)by * bw[0] + bx, 0, j.dc[c.td], j.ac[c.ta], pred[0]);
       }
     return 0;
   }
@@ -442,7 +533,7 @@ int walk_blocks(Jpeg& j, OnBlock&& on_block, OnSkip&& on_skip) {
         const Comp& c = j.comp[ci];
         for (int yy = 0; yy < c.v; ++yy)
           for (int xx = 0; xx < c.h; ++xx)
-            on_block(b, base[ci] + (int64_t)(my * c.v + yy) * bw[ci] + mx * c.h + xx, j.dc[c.td], j.ac[c.ta],
+            on_block(b, base[ci] + (int64_t)(my * c.v + yy) * bw[ci] + mx * c.h + xx, ci, j.dc[c.td], j.ac[c.ta],
                      pred[ci]);
       }
     }
@@ -450,9 +541,12 @@ int walk_blocks(Jpeg& j, OnBlock&& on_block, OnSkip&& on_skip) {
 }
 
 // Packed block record (mmf_jpeg_entropy_packed): uint64 mask of the nonzero ZIGZAG positions, then
-// their int16 values in zigzag (= decode) order, padded to 8 bytes.  Returns the record's bytes.
-inline int decode_block_packed(Bits& b, const Huff& dc, const Huff& ac, int& pred, uint8_t* rec) {
+// their int16 values in zigzag (= decode) order, padded to 8 bytes.  Returns the record's bytes;
+// *absum = the sum of |coef * q| over the block (qz: its table in zigzag order), the range prefilter.
+inline int decode_block_packed(Bits& b, const Huff& dc, const Huff& ac, int& pred, uint8_t* rec, const uint16_t* qz,
+                               int64_t* absum) {
   uint64_t mask = 0;
+  int64_t sum = 0;
   int16_t* val = reinterpret_cast<int16_t*>(rec + 8);
   int n = 0;
   int t = decode_sym(b, dc);
@@ -465,6 +559,8 @@ inline int decode_block_packed(Bits& b, const Huff& dc, const Huff& ac, int& pre
   if (pred) {
     mask = 1;
     val[n++] = (int16_t)pred;
+    const int dcv = (int16_t)pred;
+    sum = (int64_t)(dcv < 0 ? -dcv : dcv) * qz[0];
   }
   for (int k = 1; k < 64; ++k) {
     if (b.n < 16) b.fill();
@@ -490,7 +586,10 @@ inline int decode_block_packed(Bits& b, const Huff& dc, const Huff& ac, int& pre
     if (k > 63) break;  // corrupt run past the block: libjpeg drops the coefficient
     mask |= 1ull << k;  // (k only grows: each position is written at most once)
     val[n++] = (int16_t)v;
+    const int av = (int16_t)v;
+    sum += (int64_t)(av < 0 ? -av : av) * qz[k];
   }
+  *absum = sum;
   memcpy(rec, &mask, 8);
   for (int i = n; i & 3; ++i) val[i] = 0;  // deterministic padding
   return (8 + 2 * n + 7) & ~7;
@@ -721,6 +820,17 @@ int decode_progressive(Jpeg& j, int16_t* coefs, uint64_t* nzm) {
   return 0;
 }
 
+// every block of dense planes (components back to back) inside the exact range?
+bool planes_in_range(const Jpeg& j, const int16_t* coefs) {
+  const int16_t* blk = coefs;
+  for (int c = 0; c < j.ncomp; ++c) {
+    const int64_t nb = (int64_t)j.mcux * j.comp[c].h * j.mcuy * j.comp[c].v;
+    for (int64_t b = 0; b < nb; ++b, blk += 64)
+      if (!dense_block_in_range(blk, j.qt[j.comp[c].tq])) return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" int mmf_jpeg_entropy(const uint8_t* data, int64_t nbytes, int16_t* coefs, uint16_t* qt) {
@@ -735,11 +845,19 @@ extern "C" int mmf_jpeg_entropy(const uint8_t* data, int64_t nbytes, int16_t* co
     memset(coefs, 0, blocks * 128);
     thread_local std::vector<uint64_t> nzm;
     if ((int64_t)nzm.size() < blocks) nzm.resize(blocks);
-    return decode_progressive(j, coefs, nzm.data());
+    const int prc = decode_progressive(j, coefs, nzm.data());
+    if (prc) return prc;
+    return planes_in_range(j, coefs) ? 0 : MMF_EUNSUPPORTED;
   }
-  return walk_blocks(
-      j, [&](Bits& b, int64_t gb, const Huff& dc, const Huff& ac, int& pred) { decode_block(b, dc, ac, pred, coefs + gb * 64); },
+  bool inside = true;
+  walk_blocks(
+      j,
+      [&](Bits& b, int64_t gb, int ci, const Huff& dc, const Huff& ac, int& pred) {
+        decode_block(b, dc, ac, pred, coefs + gb * 64);
+        if (inside) inside = dense_block_in_range(coefs + gb * 64, j.qt[j.comp[ci].tq]);
+      },
       [&](int64_t gb) { memset(coefs + gb * 64, 0, 128); });
+  return inside ? 0 : MMF_EUNSUPPORTED;
 }
 
 extern "C" int64_t mmf_jpeg_packed_bound(int32_t blocks) { return 8 + (int64_t)blocks * (8 + 128); }
@@ -767,6 +885,7 @@ extern "C" int mmf_jpeg_entropy_packed(const uint8_t* data, int64_t nbytes, uint
     memset(dense.data(), 0, blocks * 128);
     const int prc = decode_progressive(j, dense.data(), nzm.data());
     if (prc) return prc;
+    if (!planes_in_range(j, dense.data())) return MMF_EUNSUPPORTED;
     for (int64_t b = 0; b < blocks; ++b) {
       const int16_t* blk = dense.data() + b * 64;
       const int sz = pack_block(blk, nzm[b] | (uint64_t)(blk[0] != 0), out + cur);
@@ -776,15 +895,20 @@ extern "C" int mmf_jpeg_entropy_packed(const uint8_t* data, int64_t nbytes, uint
     *used = cur;
     return 0;
   }
+  bool inside = true;
   walk_blocks(
       j,
-      [&](Bits& b, int64_t gb, const Huff& dc, const Huff& ac, int& pred) {
+      [&](Bits& b, int64_t gb, int ci, const Huff& dc, const Huff& ac, int& pred) {
+        const int tq = j.comp[ci].tq;
+        int64_t absum;
         block_off[gb] = (uint32_t)cur;
-        cur += decode_block_packed(b, dc, ac, pred, out + cur);
+        const int sz = decode_block_packed(b, dc, ac, pred, out + cur, j.qz[tq], &absum);
+        if (absum > kRangePrefilter && inside) inside = record_in_range(out + cur, j.qt[tq]);
+        cur += sz;
       },
       [&](int64_t gb) { block_off[gb] = 0; });
   *used = cur;
-  return 0;
+  return inside ? 0 : MMF_EUNSUPPORTED;
 }
 
 extern "C" int mmf_jpeg_stage_packed(const uint8_t* data, int64_t nbytes, uint8_t* dst, int64_t dst_cap,

@@ -12,7 +12,10 @@ Progressive files are decoded scan by scan into the same coefficients.  Files th
 not take (CMYK, 4:4:0, lossless / arithmetic / 12-bit, RGB-id files, files whose data ends before
 the EOI marker, ...) report MMF_EUNSUPPORTED and are decoded by Pillow on the host, as before (so a
 truncated file raises Pillow's "image file is truncated", as in the reference); so are images past
-the device resampler's tap budget.
+the device resampler's tap budget.  One decline is known only after entropy decoding: a file whose
+dequantised coefficients leave the range in which the device's integer IDCT equals Pillow's
+(rewritten quantisation tables; jpeg_host.cpp block_in_range) comes back MMF_EUNSUPPORTED from the
+staging call; the stager drops it from the chunk and stages the rest once more.
 """
 from __future__ import annotations
 
@@ -99,10 +102,31 @@ class JpegStager:
         for i in np.flatnonzero(ok):
             if not lib.mmf_resize_supported(int(allinf[i, 0]), int(allinf[i, 1])):
                 ok[i] = False
-        st.index = np.flatnonzero(ok).tolist()
+        if not ok.any():
+            return st
+        slot = self.next_slot
+        self.next_slot ^= 1
+        if self.copied[slot] is not None:
+            self.copied[slot].synchronize()  # the previous H2D from this slot has finished
+        while True:
+            st = Staged()
+            declined = self._stage_files(st, datas, allinf, np.flatnonzero(ok).tolist(), slot)
+            if not declined:
+                return st
+            # files whose coefficients leave the range in which the device IDCT equals Pillow's
+            # (jpeg_host.cpp: rewritten quantisation tables) are known only after entropy decoding:
+            # they go to Pillow like a header decline, and the rest of the chunk is staged once more
+            ok[declined] = False
+
+    def _stage_files(self, st: Staged, datas, allinf, index: List[int], slot: int) -> List[int]:
+        """Entropy-decode datas[index] into pinned slot `slot` and fill st; returns the chunk positions
+        the decoder declined (MMF_EUNSUPPORTED) -- st is then incomplete and the caller stages the
+        chunk again without them."""
+        lib = self.lib
+        st.index = index
         n = len(st.index)
         if n == 0:
-            return st
+            return []
         inf = np.ascontiguousarray(allinf[st.index])
         blocks = inf[:, 11].astype(np.int64)
         pixels = inf[:, 0].astype(np.int64) * inf[:, 1]
@@ -121,11 +145,7 @@ class JpegStager:
         sec["packed"] = off
         st.sections, st.infos = sec, inf
         st.out_off = out_off
-        slot = self.next_slot
-        self.next_slot ^= 1
         st.slot = slot
-        if self.copied[slot] is not None:
-            self.copied[slot].synchronize()  # the previous H2D from this slot has finished
         # the packed records' size is known only after decoding: start from ~half the dense size
         guess = off + st.blocks * self.guess_bytes_per_block
         if self.buf[slot] is None or self.buf[slot].numel() < guess:
@@ -157,6 +177,9 @@ class JpegStager:
             rcs_a = np.array(list(self._pool.map(entropy, range(n))) if n > 1 else [entropy(0)], np.int32)
         rcs = rcs_a.tolist()
         overflow = [k for k, rc in enumerate(rcs) if rc == MMF_ERANGE]
+        declined = [st.index[k] for k, rc in enumerate(rcs) if rc == MMF_EUNSUPPORTED]
+        if declined:
+            return declined
         bad = [k for k, rc in enumerate(rcs) if rc not in (0, MMF_ERANGE)]
         if bad:  # (a header that parsed but a scan that did not: never seen; decode those on the host)
             raise hip.MMFError(f"mmf_jpeg_stage_packed failed for chunk positions {[st.index[k] for k in bad]}")
@@ -180,7 +203,7 @@ class JpegStager:
                 host[o:o + used.value] = scratch[:used.value]
         host[sec["pk_off"]:sec["pk_off"] + n * 8] = pk_off.view(np.uint8)
         st.nbytes = total
-        return st
+        return []
 
 
 def _reconstruct(lib, h, p, st: Staged, samples: int, rgbx: int) -> int:

@@ -11,7 +11,8 @@ algorithms:
     edges, jdmainct.c make_funny_pointers / set_bottom_pointers);
   * jdcolor.c ycc_rgb_convert with build_ycc_rgb_table (SCALEBITS 16).
 Pinned against Pillow itself in this container (tests/test_jpeg_cpu.py: bit-exact pixels on every
-case); the host entropy decoder (csrc/jpeg_host.cpp) and the device reconstruction (csrc/jpeg.hip)
+case inside in_exact_range -- outside it, where table[v & 1023] stops being a clamp, Pillow's SIMD
+IDCT saturates and this restatement, like the C code it restates, does not); the host entropy decoder (csrc/jpeg_host.cpp) and the device reconstruction (csrc/jpeg.hip)
 are checked against this restatement and against Pillow.
 
 Supported: 8-bit baseline sequential (SOF0/SOF1) Huffman JPEGs with 1 component or 3 YCbCr
@@ -290,16 +291,40 @@ def _range_limit(v):
     return np.where(m < 128, m + 128, np.where(m < 512, 255, np.where(m < 896, 0, m - 896)))
 
 
-def idct_islow(coef, qt):
-    """coef int [..., 64] natural order, qt [64] -> uint8 [..., 8, 8] samples.  (The zero-AC
-    shortcuts of jidctint.c give the same values as the full computation.)"""
-    c = coef.astype(np.int64) * qt.astype(np.int64)
-    c = c.reshape(coef.shape[:-1] + (8, 8))  # [row (v), col (u)]
+def _idct_passes(coef, qt):
+    """coef int [..., 64] natural order, qt [64] -> (dequantised [..., 64], pass-1 workspace
+    [..., 8, 8], pass-2 output before the range limit [..., 8, 8]), all int64 -- the integers of
+    jidctint.c in 64-bit arithmetic.  (Its zero-AC shortcuts give the same values.)"""
+    d = coef.astype(np.int64) * qt.astype(np.int64)
+    c = d.reshape(coef.shape[:-1] + (8, 8))  # [row (v), col (u)]
     cols = _idct_1d(*[c[..., r, :] for r in range(8)], CONST_BITS - PASS1_BITS, False)  # per column
     ws = np.stack(cols, axis=-2)  # [..., row, col]
     rows = _idct_1d(*[ws[..., :, k] for k in range(8)], CONST_BITS + PASS1_BITS + 3, True)
-    out = np.stack(rows, axis=-1)
-    return _range_limit(out).astype(np.uint8)
+    return d, ws, np.stack(rows, axis=-1)
+
+
+def idct_islow(coef, qt):
+    """coef int [..., 64] natural order, qt [64] -> uint8 [..., 8, 8] samples."""
+    return _range_limit(_idct_passes(coef, qt)[2]).astype(np.uint8)
+
+
+def in_exact_range(coefs, info) -> bool:
+    """True when every block of the file (coefs = entropy_decode's planes, the MCU-padded grid) keeps
+    the integer IDCT inside the range where this restatement, the C islow IDCT, libjpeg-turbo's SIMD
+    islow IDCT (16-bit lanes, then a saturating clamp) and the device kernel (32-bit) all agree:
+      1. |coef * q| <= 32767 (the dequantised value fits a 16-bit lane),
+      2. |pass-1 workspace| <= 32767,
+      3. -512 <= pass-2 output <= 511: table[v & 1023] is a clamp only there (v = 512 wraps to 0).
+    Files Pillow's own encoder writes stay far inside; a file whose quantisation tables were
+    rewritten need not.  The product declines files outside (csrc/jpeg_host.cpp states the same
+    predicate) and Pillow decodes them."""
+    for (cid, h, v, tq), cf in zip(info.comps, coefs):
+        d, ws, out = _idct_passes(cf, info.qt[tq])
+        if np.abs(d).max(initial=0) > 32767 or np.abs(ws).max(initial=0) > 32767:
+            return False
+        if out.min(initial=0) < -512 or out.max(initial=0) > 511:
+            return False
+    return True
 
 
 def component_planes(coefs, info):
@@ -358,8 +383,14 @@ def decode(data: bytes) -> np.ndarray:
         raise NotImplementedError(f"{n} components")
     if n == 3 and info.adobe is not None and info.adobe == 0:
         raise NotImplementedError("Adobe RGB (untransformed) JPEG")
+    return reconstruct(entropy_decode(data, info), info)
+
+
+def reconstruct(coefs, info) -> np.ndarray:
+    """Quantised coefficient planes (entropy_decode's) -> uint8 [H, W, 3]: IDCT, fancy upsampling,
+    YCbCr -> RGB (what the device kernels compute from the same planes)."""
+    n = len(info.comps)
     hmax, vmax, _, _ = geometry(info)
-    coefs = entropy_decode(data, info)
     planes = component_planes(coefs, info)
     W, H = info.width, info.height
     if n == 1:

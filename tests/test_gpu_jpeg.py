@@ -171,3 +171,113 @@ def test_analyze_pairs_oversized_and_truncated_jpegs(forensics, golden_inputs):
     cut = items[0][:len(items[0]) * 2 // 3]
     with pytest.raises(OSError, match="truncated"):
         forensics.analyze_pairs(texts[:2], [items[2], cut])
+
+
+# ---- files whose quantisation tables were rewritten (tests/jpeg_cases.py hostile_tables): inside the
+# restatement's range predicate the device decodes them as Pillow does; outside, the host decoder
+# declines them after entropy decoding and the stager leaves them to Pillow.
+
+def _in_range(seq, _cache={}):
+    from oracle import jpeg_decode as J
+    info = J.parse(seq)
+    key = seq[info.scan_data_at:]
+    if key not in _cache:
+        _cache[key] = J.entropy_decode(seq, info)
+    return J.in_exact_range(_cache[key], info)
+
+
+def test_hostile_and_extreme_files_staged_exactly_when_in_range(engine, stager):
+    """Every hostile_tables() and extreme_legit() file, in chunks that mix both kinds: the stager keeps
+    exactly the files inside the range, and their device pixels equal Pillow's."""
+    from mmf_amd import jpeg
+    files = [(n, d, _in_range(seq)) for n, d, seq in C.hostile_tables()]
+    files += [(n, d, True) for n, d in C.extreme_legit()]
+    assert sum(i for _, _, i in files) >= 140 and sum(not i for _, _, i in files) >= 100
+    for a in range(0, len(files), 64):
+        chunk = files[a:a + 64]
+        st = stager.stage([d for _, d, _ in chunk])
+        assert st.index == [k for k, (_, _, inside) in enumerate(chunk) if inside], [n for n, _, _ in chunk]
+        for k, g in zip(st.index, jpeg.device_rgb(engine, stager, st)):
+            np.testing.assert_array_equal(g, C.pillow_rgb(chunk[k][1]), err_msg=chunk[k][0])
+
+
+@pytest.mark.parametrize("batch_call", [True, False])
+def test_stager_drops_out_of_range_files_and_restages(engine, batch_call):
+    """A chunk of [good, hostile outside, good, hostile inside] (and one where every file is
+    declined): st.index == [0, 2, 3], the staged tables, block offsets and records equal per-file
+    staging, the pixels equal Pillow's -- by the chunk call and by the per-file pool calls."""
+    import ctypes
+
+    from mmf_amd import jpeg
+    hostile = C.hostile_tables()
+    out = [d for _, d, seq in hostile if not _in_range(seq)]
+    ins = [d for n, d, seq in hostile if _in_range(seq) and "-x1" not in n]
+    good = [d for _, d in C.supported_jpegs()[:2]]
+    chunk = [good[0], out[0], good[1], ins[-1]]
+    s = jpeg.JpegStager(workers=3)
+    s.batch_call = batch_call
+    try:
+        assert s.stage([out[0], None, out[-1]]).index == []
+        for files, want in ((chunk, [0, 2, 3]), ([out[1]] + chunk + [out[2]], [1, 3, 4])):
+            st = s.stage(files)
+            assert st.index == want
+            host, sec, lib = s.buf[st.slot].numpy(), st.sections, engine.lib
+            pk_off = host[sec["pk_off"]:sec["pk_off"] + 8 * len(want)].view(np.int64)
+            base = 0
+            for k, i in enumerate(want):
+                d, blocks = files[i], int(st.infos[k, 11])
+                ref = np.zeros(int(lib.mmf_jpeg_packed_bound(blocks)), np.uint8)
+                boff = np.zeros(blocks, np.uint32)
+                qt = np.zeros(192, np.uint16)
+                used = ctypes.c_int64(0)
+                assert lib.mmf_jpeg_entropy_packed(d, len(d), ref.ctypes.data, ref.size, boff.ctypes.data,
+                                                   qt.ctypes.data, ctypes.byref(used)) == 0
+                o = sec["packed"] + int(pk_off[k])
+                np.testing.assert_array_equal(host[o:o + used.value], ref[:used.value])
+                o = sec["block_off"] + 4 * base
+                np.testing.assert_array_equal(host[o:o + 4 * blocks].view(np.uint32), boff)
+                ncomp = int(st.infos[k, 2])
+                o = sec["qt"] + 384 * k
+                np.testing.assert_array_equal(host[o:o + 128 * ncomp].view(np.uint16), qt[:64 * ncomp])
+                base += blocks
+            assert st.blocks == base
+            for i, g in zip(want, jpeg.device_rgb(engine, s, st)):
+                np.testing.assert_array_equal(g, C.pillow_rgb(files[i]))
+    finally:
+        s.close()
+
+
+def test_analyze_pairs_on_rewritten_tables(forensics, golden_inputs):
+    """analyze_pairs over chunks that mix ordinary files with rewritten-table files inside and outside
+    the range (sequential and progressive, a 16-bit table): device_jpeg=True equals device_jpeg=False
+    dict for dict -- the files outside reach Pillow in both."""
+    imgs = golden_inputs["imgs"]
+    n = imgs.shape[0]
+    lib = forensics.engine.lib
+    items = []
+    for i in range(10):
+        a = imgs[i % n]
+        base = C.encode(a, quality=(90, 75, 50)[i % 3], subsampling=2 if i % 2 else 0, progressive=i in (4, 7))
+        scale = (1, 2, 16, 3, 2, 1, 64, 4, 2, 255)[i]
+        if i == 8:
+            items.append(C.rewrite_dqt(base, lambda tq, q: np.r_[q[:1], q[1:] * 300], sixteen=True))
+        else:
+            items.append(C.rewrite_dqt(base, lambda tq, q, s=scale: np.minimum(q * s, 255)) if scale > 1 else base)
+    info = np.zeros(16, np.int32)
+    codes = []
+    for d in items:
+        assert lib.mmf_jpeg_header(d, len(d), info.ctypes.data) == 0
+        co = np.zeros((int(info[11]), 64), np.int16)
+        qt = np.zeros(192, np.uint16)
+        codes.append(lib.mmf_jpeg_entropy(d, len(d), co.ctypes.data, qt.ctypes.data))
+    assert codes == [0, 0, -95, 0, 0, 0, -95, -95, -95, -95]  # the last chunk of 4 is declined whole
+    texts = [f"sample text {i % n}" for i in range(10)]
+    forensics.device_jpeg = True
+    dev = forensics.analyze_pairs(texts, items)
+    forensics.device_jpeg = False
+    try:
+        host = forensics.analyze_pairs(texts, items)
+    finally:
+        forensics.device_jpeg = True
+    assert len(dev) == 10
+    assert dev == host

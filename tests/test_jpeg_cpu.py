@@ -326,3 +326,208 @@ def test_rgb_component_ids_go_to_pillow():
                 e[a + (10 + 3 * k if m == 0xC0 else 5 + 2 * k)] = k + 1
     assert L.mmf_jpeg_header(bytes(e), len(e), info.ctypes.data) == 0
     assert not np.array_equal(C.pillow_rgb(bytes(e)), px)
+
+
+# ---- the exact range: files whose quantisation tables were rewritten (tests/jpeg_cases.py
+# hostile_tables) push the integer IDCT past the point where table[v & 1023] is a clamp; the
+# restatement's predicate (oracle in_exact_range) says which files still decode as Pillow does, and
+# the host entropy decoders decline exactly the others.
+
+HOSTILE = C.hostile_tables()
+LEGIT = C.extreme_legit()
+_coefs = {}
+
+
+def coefs_of(seq):
+    """(entropy-decoded planes, info) of a sequential file; files that share their entropy-coded data
+    (rewritten tables) share the planes."""
+    info = J.parse(seq)
+    key = seq[info.scan_data_at:]
+    if key not in _coefs:
+        _coefs[key] = J.entropy_decode(seq, info)
+    return _coefs[key], info
+
+
+def host_codes(L, d):
+    """Return codes of the three host entropy entry points (dense, packed, staged) and of the batch
+    form, plus the bytes the staging call reserved."""
+    info = np.zeros(16, np.int32)
+    assert L.mmf_jpeg_header(d, len(d), info.ctypes.data) == 0
+    blocks = int(info[11])
+    co = np.zeros((blocks, 64), np.int16)
+    qt = np.zeros((3, 64), np.uint16)
+    bound = int(L.mmf_jpeg_packed_bound(blocks))
+    packed = np.zeros(bound, np.uint8)
+    boff = np.zeros(blocks, np.uint32)
+    used = ctypes.c_int64(0)
+    cursor = np.zeros(1, np.int64)
+    off = np.zeros(1, np.int64)
+    rcs = [L.mmf_jpeg_entropy(d, len(d), co.ctypes.data, qt.ctypes.data),
+           L.mmf_jpeg_entropy_packed(d, len(d), packed.ctypes.data, bound, boff.ctypes.data, qt.ctypes.data,
+                                     ctypes.byref(used)),
+           L.mmf_jpeg_stage_packed(d, len(d), packed.ctypes.data, bound, cursor.ctypes.data, boff.ctypes.data,
+                                   qt.ctypes.data, off.ctypes.data)]
+    reserved = int(cursor[0])
+    ptrs = (ctypes.c_char_p * 1)(d)
+    lens = np.array([len(d)], np.int64)
+    base = np.zeros(1, np.int64)
+    rc1 = np.full(1, 7, np.int32)
+    cursor[0] = 0
+    assert L.mmf_jpeg_stage_packed_batch(ctypes.cast(ptrs, ctypes.c_void_p), lens.ctypes.data, 1, packed.ctypes.data,
+                                         bound, cursor.ctypes.data, boff.ctypes.data, base.ctypes.data,
+                                         qt.ctypes.data, off.ctypes.data, 2, rc1.ctypes.data) == 0
+    return rcs + [int(rc1[0])], reserved
+
+
+@pytest.mark.parametrize("name,data,seq", HOSTILE, ids=[n for n, _, _ in HOSTILE])
+def test_hostile_tables_in_range_decode_as_pillow_and_host_declines_the_rest(name, data, seq):
+    """Inside the predicate the restatement (the arithmetic of the device kernels) equals Pillow;
+    the host decoders return 0 exactly there and MMF_EUNSUPPORTED outside, from every entry point,
+    and a declined file reserves no staging room."""
+    co, info = coefs_of(seq)
+    inside = J.in_exact_range(co, info)
+    if inside:
+        np.testing.assert_array_equal(J.reconstruct(co, info), C.pillow_rgb(data))
+    rcs, reserved = host_codes(lib(), data)
+    assert rcs == [0 if inside else -95] * 4
+    assert (reserved > 0) == inside
+
+
+def test_hostile_family_is_not_vacuous():
+    """At least 100 of the rewritten files are inside the range and at least 100 outside (195 / 213
+    with Pillow 12.2's encoder), and outside the restatement really differs from Pillow: the decline
+    is what keeps the device path's pixels Pillow's."""
+    inside = [J.in_exact_range(*coefs_of(seq)) for _, _, seq in HOSTILE]
+    assert sum(inside) >= 100 and len(inside) - sum(inside) >= 100
+    differ = sum(not np.array_equal(J.reconstruct(*coefs_of(seq)), C.pillow_rgb(d))
+                 for (_, d, seq), i in zip(HOSTILE, inside) if not i)
+    assert differ >= 100
+    kinds = {n.split("-")[0] for (n, _, _), i in zip(HOSTILE, inside) if i}
+    assert {"prog", "gray", "dconly", "pq1"} <= kinds  # each added kind has accepted files
+    kinds = {n.split("-")[0] for (n, _, _), i in zip(HOSTILE, inside) if not i}
+    assert {"prog", "gray", "dconly", "pq1"} <= kinds  # ... and declined ones
+
+
+@pytest.mark.parametrize("name,data", LEGIT, ids=[n for n, _ in LEGIT])
+def test_extreme_legitimate_files_are_in_range(name, data):
+    """Unmodified encoder output at its coefficient extremes (noise, saturated noise, checkerboards,
+    quality 1 .. 100): inside the range, equal to Pillow, accepted by every host entry point."""
+    co, info = coefs_of(data)
+    assert J.in_exact_range(co, info)
+    np.testing.assert_array_equal(J.reconstruct(co, info), C.pillow_rgb(data))
+    assert host_codes(lib(), data)[0] == [0, 0, 0, 0]
+
+
+def test_supported_and_progressive_cases_are_in_range():
+    """The decline never touches the ordinary files: every SUPPORTED case and the sequential twin of
+    every PROGRESSIVE case (the same coefficients) is inside the range, and the host accepts all."""
+    L = lib()
+    for name, d in CASES:
+        assert J.in_exact_range(*coefs_of(d)), name
+    for name, prog, seq in C.progressive_pairs():
+        assert J.in_exact_range(*coefs_of(seq)), name
+        assert host_codes(L, prog)[0] == [0, 0, 0, 0], name
+
+
+def _gray_file(blocks, q=None):
+    """A one-row grayscale file of the given dequantised-by-q blocks ([n][64] natural order)."""
+    blocks = np.asarray(blocks, np.int64)
+    qt = np.ones(64, np.int64) if q is None else q
+    return C.encode_coefficients(8 * len(blocks), 8, None, [qt], [blocks[None]])
+
+
+@pytest.mark.parametrize("d,inside", [(4083, True), (4091, True), (4092, False), (4100, False),
+                                      (-4092, True), (-4100, True), (-4101, False), (-4110, False)])
+def test_range_boundary_is_sharp_on_a_dc_only_block(d, inside):
+    """A DC-only block decodes to the flat sample (d + 4) >> 3: 511 at d = 4091 (inside, Pillow's
+    clamp and the table agree on 255), 512 at d = 4092 (the table wraps to 0: outside); -512 at
+    d = -4100, -513 at d = -4101."""
+    blk = np.zeros((2, 64), np.int64)
+    blk[1, 0] = d  # the first block stays zero: the file as a whole is judged by its worst block
+    f = _gray_file(blk)
+    co, info = coefs_of(f)
+    _, _, out = J._idct_passes(co[0], info.qt[0])
+    assert out[0, 1].min() == out[0, 1].max() == (d + 4) >> 3
+    assert J.in_exact_range(co, info) == inside
+    assert host_codes(lib(), f)[0] == [0 if inside else -95] * 4
+    if inside:
+        np.testing.assert_array_equal(J.decode(f), C.pillow_rgb(f))
+    else:
+        assert not np.array_equal(J.decode(f), C.pillow_rgb(f))
+
+
+def test_host_predicate_around_the_prefilter_bound():
+    """The host skips the exact test for blocks with sum |coef q| <= 2036 (|sample| <= sum / 4).  Blocks
+    that put all of that on one coefficient, or spread it with the signs that add up at one pixel,
+    cross first the prefilter bound and then the real range: the host's answer equals the
+    restatement's on both sides of each."""
+    L = lib()
+    rng = np.random.default_rng(5)
+    yy, xx = np.mgrid[0:8, 0:8]
+    seen = set()
+    for total in (2000, 2036, 2037, 2100, 2200, 2400, 3000, 4000):
+        blocks = []
+        for nat in (0, 1, 9, 63, 36):
+            b = np.zeros(64, np.int64)
+            b[nat] = total
+            blocks += [b, -b]
+        for _ in range(6):  # |d| spread over the block, signed like the basis functions at pixel (y, x)
+            y, x = rng.integers(0, 8, 2)
+            w = rng.random(64) ** 3
+            mag = np.floor(w / w.sum() * total).astype(np.int64)
+            mag[0] += total - mag.sum()
+            sign = np.sign(np.cos((2 * y + 1) * yy * np.pi / 16) * np.cos((2 * x + 1) * xx * np.pi / 16)).reshape(64)
+            blocks.append((mag * np.where(sign == 0, 1, sign)).astype(np.int64))
+        for b in blocks:
+            assert np.abs(b).sum() == total
+            f = _gray_file([b])
+            inside = J.in_exact_range(*coefs_of(f))
+            assert inside or total > 2036  # the prefilter's claim
+            assert host_codes(L, f)[0] == [0 if inside else -95] * 4
+            seen.add((total > 2036, inside))
+    assert seen == {(False, True), (True, True), (True, False)}
+
+
+def test_sixteen_bit_tables_and_large_values_inside_the_range():
+    """val = +-1023 with q = 1 on one position (samples within +-1023 / 4) and coef = +-1 with a 16-bit
+    table of 4000 for DC ((4000 + 4) >> 3 = 500) and 2000 for AC (within +-2000 / 4) are legal and
+    inside the range; 4200 for DC (525) is outside."""
+    L = lib()
+    big = np.zeros((4, 64), np.int64)
+    big[0, 1], big[1, 8], big[2, 63], big[3, 0] = 1023, -1023, 1023, -1023
+    f = _gray_file(big)
+    assert J.in_exact_range(*coefs_of(f)) and host_codes(L, f)[0] == [0] * 4
+    np.testing.assert_array_equal(J.decode(f), C.pillow_rgb(f))
+    one = np.zeros((4, 64), np.int64)
+    one[0, 0], one[1, 0], one[2, 9], one[3, 63] = 1, -1, 1, -1
+    f = C.rewrite_dqt(_gray_file(one), lambda tq, q: np.r_[4000, np.full(63, 2000)], sixteen=True)
+    co, info = coefs_of(f)
+    assert info.qt[0].max() == 4000 and J.in_exact_range(co, info) and host_codes(L, f)[0] == [0] * 4
+    np.testing.assert_array_equal(J.decode(f), C.pillow_rgb(f))
+    f = C.rewrite_dqt(_gray_file(one), lambda tq, q: np.r_[4200, np.full(63, 2000)], sixteen=True)
+    assert not J.in_exact_range(*coefs_of(f)) and host_codes(L, f)[0] == [-95] * 4
+
+
+def test_test_packer_equals_the_host_packer():
+    """tests/jpeg_refs.py pack_records (the operands of the device kernel tests) writes the host
+    decoder's record format: byte for byte on grayscale files (decode order = block order), and the
+    same blocks after unpacking on colour files."""
+    from tests import jpeg_refs as R
+    L = lib()
+    for name, d in [c for c in CASES if "-L-" in c[0]] + CASES[:4]:
+        rc, info, co, qt = c_decode(L, d)
+        assert rc == 0
+        blocks = int(info[11])
+        packed = np.zeros(int(L.mmf_jpeg_packed_bound(blocks)), np.uint8)
+        boff = np.zeros(blocks, np.uint32)
+        used = ctypes.c_int64(0)
+        assert L.mmf_jpeg_entropy_packed(d, len(d), packed.ctypes.data, packed.size, boff.ctypes.data, qt.ctypes.data,
+                                         ctypes.byref(used)) == 0
+        mine, moff = R.pack_records(co, share_zero=False)
+        np.testing.assert_array_equal(unpack(mine, moff, blocks), co)
+        if info[2] == 1 and info[5] * 8 - info[0] < 8 and info[6] * 8 - info[1] < 8:  # no padding blocks
+            np.testing.assert_array_equal(mine, packed[:used.value])
+            np.testing.assert_array_equal(moff, boff)
+        shared, soff = R.pack_records(co, share_zero=True)
+        np.testing.assert_array_equal(unpack(shared, soff, blocks), co)
+        assert len(shared) <= len(mine) and ((soff == 0) == ~co.any(1)).all()
