@@ -246,6 +246,40 @@ int mmf_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, co
 int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch, const float* params,
                               float* batch_loss, float* row_cos, void* ws, int64_t ws_bytes, void* stream);
 
+/* A hyperparameter study of the same training (run_hyperparameter_tuning, train_clip_detective.py:427-454):
+ * `trials` (1..MMF_CLIP_TRIALS_MAX) independent trainings side by side in the SAME six launches per
+ * step (three per eval batch), the trial as a third grid dimension; synchronisation stays stream
+ * order alone.  Every trial's results are bit-identical to mmf_clip_train_epoch /
+ * mmf_clip_contrastive_eval called for it alone, whatever its neighbours are.
+ *   img_feat, txt_feat: shared by all trials.
+ *   params, exp_avg, exp_avg_sq fp32 [trials][MMF_CLIP_TRIAL_STRIDE] (a trial's
+ *     MMF_CLIP_TRAIN_PARAMS values at the start of its slice); perm int32 [trials][N].
+ *   batch, lr, weight_decay, max_norm, step0, active: HOST arrays [trials], read before the call
+ *     returns.  Trials differ in batch size and so in steps: the call enqueues max ceil(N / batch[t])
+ *     steps, and a trial past its last step takes no further part.  active[t] == 0 (active may be
+ *     NULL: every trial is active): trial t takes no part at all -- not a byte of its params,
+ *     moments, outputs or workspace is written, and its other entries are not read.
+ *   step_loss, step_gnorm fp32 [trials][max_nsteps]; batch_loss fp32 [trials][max_nb]; row_cos
+ *     fp32 [trials][N]: a trial writes its first ceil(N / batch[t]) entries of a row, no others.
+ *   ws: ws_bytes >= mmf_clip_train_trials_ws_bytes(trials, 64) (0 for trials or batch_max out of
+ *     range): one image of the single-trial workspace per trial.
+ * MMF_EINVAL with nothing launched: trials outside 1..MMF_CLIP_TRIALS_MAX, N < 1, an active trial's
+ * batch outside 1..64 or step0 < 0, max_nsteps / max_nb below an active trial's step count, a NULL
+ * required pointer, a short ws, a device buffer off a 16-byte boundary. */
+#define MMF_CLIP_TRIALS_MAX 16
+#define MMF_CLIP_TRIAL_STRIDE 655364  /* MMF_CLIP_TRAIN_PARAMS rounded up to 4 floats */
+int64_t mmf_clip_train_trials_ws_bytes(int trials, int batch_max);
+int mmf_clip_train_epoch_trials(const float* img_feat, const float* txt_feat, int N, int trials, const int32_t* perm,
+                                const int32_t* batch, const double* lr, const double* weight_decay,
+                                const double* max_norm, const int32_t* step0, const int32_t* active, double beta1,
+                                double beta2, double eps, float* params, float* exp_avg, float* exp_avg_sq,
+                                float* step_loss, float* step_gnorm, int max_nsteps, void* ws, int64_t ws_bytes,
+                                void* stream);
+int mmf_clip_contrastive_eval_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                     const int32_t* batch, const int32_t* active, const float* params,
+                                     float* batch_loss, float* row_cos, int max_nb, void* ws, int64_t ws_bytes,
+                                     void* stream);
+
 /* Host-input geometry on the device (misinfo_forensics.py:249-253 and the
  * CLIPImageProcessor the reference calls at :386-401): B decoded uint8 images (HWC, pixel_bytes =
  * 3 for RGB or 4 for RGBX -- Pillow's in-memory layout --, any size up to a 47x downscale)

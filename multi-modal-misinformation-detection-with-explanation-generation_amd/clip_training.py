@@ -9,12 +9,17 @@ logit_scale.  CLIP has no dropout, so the frozen part is a pure function of the 
 * ``ClipProjectionTrainer``: one ``mmf_clip_train_epoch`` and one ``mmf_clip_contrastive_eval`` call per epoch on
   the cached features, the reference's checkpoint dict on a better validation accuracy, the best projections put
   back into the engine.
-* ``train_clip_detective`` / ``python -m mmf_amd.clip_training``: the reference script's entry points (without
-  its Optuna tuning).
+* ``sample_trials`` / ``ClipProjectionTuner``: the script's ``--tune`` mode (:427-454) as a study of up to 16
+  trials per launch: epoch e of every trial still running in ONE ``mmf_clip_train_epoch_trials`` and one
+  ``mmf_clip_contrastive_eval_trials`` call, each trial bit-identical to the same trial trained alone.
+* ``train_clip_detective`` / ``run_hyperparameter_tuning`` / ``python -m mmf_amd.clip_training [--tune]``: the
+  reference script's entry points.
 
 Deviations from the reference, documented in DESIGN.md §7f: the trainer computes in fp32 (no fp16 autocast /
 GradScaler), shuffling draws from a seeded generator instead of the global RNG, and the features are cached once
-(exact: the encoders are frozen and dropout-free).
+(exact: the encoders are frozen and dropout-free).  The study draws its trials up front from a seeded generator
+(Optuna's TPE sampler suggests from earlier results, which trials that run side by side do not have), does not
+prune, and writes the winning trial's checkpoint rather than the last improving one's.
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.AdamW defaults (train_clip_detect
 N_VISUAL, N_TEXT = 512 * 768, 512 * 512
 N_PARAMS = N_VISUAL + N_TEXT + 1  # MMF_CLIP_TRAIN_PARAMS: visual | text | logit_scale
 KEYS = ("visual_projection.weight", "text_projection.weight", "logit_scale")
+TRIALS_MAX, TRIAL_STRIDE = 16, 655364  # MMF_CLIP_TRIALS_MAX, MMF_CLIP_TRIAL_STRIDE (floats from one trial to the next)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -224,18 +230,22 @@ class ClipProjectionTrainer:
             if val_acc > best_acc:  # :384
                 best_acc, best = val_acc, split_heads(params)
                 if checkpoint_path:
-                    # the reference steps its scheduler before it saves (:379, :390): epoch + 1 steps, and the
-                    # optimizer's group already holds the next epoch's learning rate
-                    sched = _scheduler_state(self.epochs, self.lr, epoch + 1)
-                    torch.save({"epoch": epoch,
-                                "model_state_dict": self._model_state(best),
-                                "optimizer_state_dict": optimizer_state_dict(m, v, step0, float(sched["_last_lr"][0]),
-                                                                             self.lr, self.weight_decay),
-                                "scheduler_state_dict": sched,
-                                "val_loss": val_loss, "val_accuracy": val_acc, "train_loss": train_loss},
-                               checkpoint_path)
+                    torch.save(self._checkpoint(history[-1], best, m, v, step0), checkpoint_path)
         self._install(best if best is not None else split_heads(params))
         return history
+
+    def _checkpoint(self, entry: dict, heads: Dict[str, torch.Tensor], m, v, steps: int) -> dict:
+        """The reference's checkpoint dict (:387-397) after the epoch of history entry `entry`, `steps` optimizer
+        steps in.  The reference steps its scheduler before it saves (:379, :390): epoch + 1 steps, and the
+        optimizer's group already holds the next epoch's learning rate."""
+        sched = _scheduler_state(self.epochs, self.lr, entry["epoch"] + 1)
+        return {"epoch": entry["epoch"],
+                "model_state_dict": self._model_state(heads),
+                "optimizer_state_dict": optimizer_state_dict(m, v, steps, float(sched["_last_lr"][0]), self.lr,
+                                                             self.weight_decay),
+                "scheduler_state_dict": sched,
+                "val_loss": entry["val_loss"], "val_accuracy": entry["val_accuracy"],
+                "train_loss": entry["train_loss"]}
 
     def _model_state(self, heads: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """CLIPDetective.state_dict(): the CLIPModel under ``clip.`` with the trained tensors."""
@@ -259,14 +269,130 @@ class ClipProjectionTrainer:
 
 
 # ---------------------------------------------------------------------------------------------
+# the study
+# ---------------------------------------------------------------------------------------------
+LR_RANGE, BATCH_SIZES, EPOCH_RANGE = (1e-5, 1e-3), (8, 12, 16), (5, 15)  # train_clip_detective.py:281-283
+
+
+def sample_trials(n_trials: int, seed: int = 0) -> List[dict]:
+    """`n_trials` draws from the reference's search space: lr log-uniform in [1e-5, 1e-3], batch_size one of
+    8 / 12 / 16, epochs an integer in 5..15, from ``numpy.random.default_rng(seed)``."""
+    g = np.random.default_rng(int(seed))
+    lo, hi = np.log(LR_RANGE[0]), np.log(LR_RANGE[1])
+    out = []
+    for _ in range(int(n_trials)):
+        lr = float(np.clip(np.exp(g.uniform(lo, hi)), *LR_RANGE))
+        out.append({"lr": lr, "batch_size": int(g.choice(BATCH_SIZES)),
+                    "epochs": int(g.integers(EPOCH_RANGE[0], EPOCH_RANGE[1] + 1))})
+    return out
+
+
+class ClipProjectionTuner:
+    """run_hyperparameter_tuning's study (train_clip_detective.py:427-454) on cached features.  Trials run in
+    groups of up to 16; within a group, epoch e is one training call over the trials that still have an epoch e
+    and one validation call.  Every trial starts from the forensics' current heads and follows its own
+    ``plan(N, epochs, lr, seed)``; its bookkeeping is ``ClipProjectionTrainer.fit``'s, so its history is the one
+    ``fit`` gives for it alone.  A trial's value is the validation loss at its best-accuracy epoch (:385, :424),
+    ``inf`` when no epoch improved or a loss turned non-finite; the study minimises it, ties to the lower number."""
+
+    def __init__(self, forensics, trials: Optional[Sequence[dict]] = None, n_trials: int = 10, seed: int = 0,
+                 weight_decay: float = 0.01, max_norm: float = 1.0):
+        self.forensics, self.seed = forensics, int(seed)
+        self.weight_decay, self.max_norm = float(weight_decay), float(max_norm)
+        self.trials = [dict(t) for t in (sample_trials(n_trials, seed) if trials is None else trials)]
+        if not self.trials:
+            raise ValueError("a study needs at least one trial")
+        for i, t in enumerate(self.trials):
+            if not (1 <= int(t["batch_size"]) <= 64 and int(t["epochs"]) >= 1 and float(t["lr"]) > 0):
+                raise ValueError(f"trial {i}: batch_size in 1..64, epochs >= 1 and lr > 0 expected, got {t}")
+
+    def _trainer(self, t: dict) -> ClipProjectionTrainer:
+        """The single-trial trainer of a trial: its settings, and the checkpoint / install path."""
+        return ClipProjectionTrainer(self.forensics, batch_size=t["batch_size"], epochs=t["epochs"], lr=t["lr"],
+                                     weight_decay=t.get("weight_decay", self.weight_decay), max_norm=self.max_norm,
+                                     seed=t.get("seed", self.seed))
+
+    def tune(self, train_feats, val_feats, val_labels, checkpoint_path: Optional[str] = None) -> dict:
+        dev = self.forensics.engine.device
+        ti, tt = (torch.from_numpy(a).to(dev) for a in ClipProjectionTrainer._feats(train_feats, "training"))
+        vi, vt = (torch.from_numpy(a).to(dev) for a in ClipProjectionTrainer._feats(val_feats, "validation"))
+        labels = np.asarray(val_labels).astype(np.int64)
+        if labels.shape != (vi.shape[0],):
+            raise ValueError(f"val_labels {labels.shape} must be [{vi.shape[0]}]")
+        start = flatten_heads(self.forensics.clip_state)
+        runs = []
+        for a in range(0, len(self.trials), TRIALS_MAX):
+            runs += self._group([self._trainer(t) for t in self.trials[a:a + TRIALS_MAX]], start, ti, tt, vi, vt, labels)
+        results = [{"number": i, "params": {k: t[k] for k in ("lr", "batch_size", "epochs")}, "value": r["value"],
+                    "history": r["history"]} for i, (t, r) in enumerate(zip(self.trials, runs))]
+        best = min(range(len(runs)), key=lambda i: (runs[i]["value"], i))
+        snap = runs[best]["best"]
+        if snap is not None:  # (none: no trial ever improved on accuracy 0, or every loss was non-finite)
+            trainer = self._trainer(self.trials[best])
+            heads = split_heads(snap["params"][:N_PARAMS])
+            if checkpoint_path:
+                torch.save(trainer._checkpoint(snap["entry"], heads, snap["m"][:N_PARAMS].cpu(),
+                                               snap["v"][:N_PARAMS].cpu(), snap["steps"]), checkpoint_path)
+            trainer._install(heads)
+        return {"best_trial": best, "best_value": runs[best]["value"], "best_params": results[best]["params"],
+                "trials": results}
+
+    def _group(self, trainers: List[ClipProjectionTrainer], start: torch.Tensor, ti, tt, vi, vt, labels) -> List[dict]:
+        """Up to 16 trials side by side -> per trial {history, value, best: the best epoch's device snapshot
+        {params, m, v, steps, entry} or None}."""
+        eng = self.forensics.engine
+        dev = eng.device
+        T, N = len(trainers), ti.shape[0]
+        params = torch.zeros(T, TRIAL_STRIDE, dtype=torch.float32, device=dev)
+        params[:, :N_PARAMS] = start.to(dev)
+        m, v = torch.zeros_like(params), torch.zeros_like(params)
+        bs = [t.batch_size for t in trainers]
+        plans = [plan(N, t.epochs, t.lr, t.seed) for t in trainers]
+        steps_per_epoch = [-(-N // b) for b in bs]
+        val_batches = [-(-len(labels) // b) for b in bs]
+        step0 = [0] * T
+        runs = [{"history": [], "value": float("inf"), "best": None, "best_acc": 0.0, "failed": False} for _ in trainers]
+        for epoch in range(max(t.epochs for t in trainers)):
+            active = [t.epochs > epoch and not r["failed"] for t, r in zip(trainers, runs)]
+            if not any(active):
+                break
+            perm = np.zeros((T, N), np.int32)
+            lr = [0.0] * T
+            for t in range(T):
+                if active[t]:
+                    perm[t], lr[t] = plans[t][epoch]
+            sl, _ = eng.clip_train_epoch_trials(ti, tt, torch.from_numpy(perm).to(dev), bs, lr, BETAS, EPS,
+                                                [t.weight_decay for t in trainers], [t.max_norm for t in trainers],
+                                                step0, params, m, v, active=active)
+            bl, cos = eng.clip_contrastive_eval_trials(vi, vt, bs, params, active=active)
+            sl, bl, cos = (x.cpu().numpy() for x in (sl, bl, cos))
+            for t in range(T):
+                if not active[t]:
+                    continue
+                step0[t] += steps_per_epoch[t]
+                train_loss = float(sl[t, :steps_per_epoch[t]].astype(np.float64).mean())
+                val_loss = float(bl[t, :val_batches[t]].astype(np.float64).mean())
+                if not (np.isfinite(train_loss) and np.isfinite(val_loss)):  # fit raises; a study goes on
+                    runs[t].update(failed=True, value=float("inf"), best=None)
+                    continue
+                accs = [batch_accuracy(cos[t, a:a + bs[t]], labels[a:a + bs[t]]) for a in range(0, len(labels), bs[t])]
+                entry = {"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss,
+                         "val_accuracy": float(np.mean(accs)), "lr": lr[t]}
+                runs[t]["history"].append(entry)
+                if entry["val_accuracy"] > runs[t]["best_acc"]:  # :384
+                    runs[t].update(best_acc=entry["val_accuracy"], value=val_loss,
+                                   best={"params": params[t].clone(), "m": m[t].clone(), "v": v[t].clone(),
+                                         "steps": step0[t], "entry": entry})
+        return runs
+
+
+# ---------------------------------------------------------------------------------------------
 # the script's entry points
 # ---------------------------------------------------------------------------------------------
-def train_clip_detective(train_csv: str = "clip_train.csv", val_csv: str = "clip_val.csv", batch_size: int = 16,
-                         epochs: int = 10, lr: float = 1e-4, device: str = "cuda", *, forensics=None, seed: int = 0,
-                         checkpoint_path: str = "clip_detective_best.pth", max_samples: Optional[int] = None):
-    """train_clip_detective.py:276-424 without the Optuna branch: training rows are the matched pairs
-    (``label == 0``, :319), validation uses every row (:322); one feature extraction per file, then the
-    trainer.  Returns the history (None when a CSV is missing)."""
+def _load_study_data(train_csv: str, val_csv: str, forensics, device: str, max_samples: Optional[int]):
+    """The script's data (train_clip_detective.py:300-330): training rows are the matched pairs (``label == 0``,
+    :319), validation uses every row (:322); one feature extraction per file.
+    -> (forensics, train_feats, val_feats, val_labels), or None when a CSV is missing."""
     import pandas as pd
     for p in (train_csv, val_csv):
         if not os.path.exists(p):
@@ -285,12 +411,45 @@ def train_clip_detective(train_csv: str = "clip_train.csv", val_csv: str = "clip
     print(f"Val samples: {len(va)}")
     train_feats = extract_features(forensics, [str(t) for t in tr["text"]], [str(p) for p in tr["image_path"]])
     val_feats = extract_features(forensics, [str(t) for t in va["text"]], [str(p) for p in va["image_path"]])
+    return forensics, train_feats, val_feats, [int(x) for x in va["label"]]
+
+
+def train_clip_detective(train_csv: str = "clip_train.csv", val_csv: str = "clip_val.csv", batch_size: int = 16,
+                         epochs: int = 10, lr: float = 1e-4, device: str = "cuda", *, forensics=None, seed: int = 0,
+                         checkpoint_path: str = "clip_detective_best.pth", max_samples: Optional[int] = None):
+    """train_clip_detective.py:276-424 without the Optuna branch (run_hyperparameter_tuning below): the script's
+    data, then the trainer.  Returns the history (None when a CSV is missing)."""
+    data = _load_study_data(train_csv, val_csv, forensics, device, max_samples)
+    if data is None:
+        return None
+    forensics, train_feats, val_feats, labels = data
     trainer = ClipProjectionTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed)
-    history = trainer.fit(train_feats, val_feats, [int(x) for x in va["label"]], checkpoint_path=checkpoint_path)
+    history = trainer.fit(train_feats, val_feats, labels, checkpoint_path=checkpoint_path)
     for h in history:
         print(f"Epoch {h['epoch'] + 1}/{epochs}  Train Loss: {h['train_loss']:.4f}  Val Loss: {h['val_loss']:.4f} | "
               f"Val Acc: {h['val_accuracy']:.4f}  Learning Rate: {h['lr']:.2e}")
     return history
+
+
+def run_hyperparameter_tuning(n_trials: int = 10, train_csv: str = "clip_train.csv", val_csv: str = "clip_val.csv", *,
+                              forensics=None, seed: int = 0, checkpoint_path: str = "clip_detective_best.pth",
+                              device: str = "cuda", max_samples: Optional[int] = None):
+    """run_hyperparameter_tuning (train_clip_detective.py:432-454): `n_trials` draws of ``sample_trials`` on one
+    feature extraction for the whole study; prints what the reference prints of its study and returns the
+    tuner's result (None when a CSV is missing)."""
+    print(f"Number of trials: {n_trials}")
+    data = _load_study_data(train_csv, val_csv, forensics, device, max_samples)
+    if data is None:
+        return None
+    forensics, train_feats, val_feats, labels = data
+    res = ClipProjectionTuner(forensics, n_trials=n_trials, seed=seed).tune(train_feats, val_feats, labels,
+                                                                            checkpoint_path=checkpoint_path)
+    print(f"Best trial: {res['best_trial']}")
+    print(f"Best val loss: {res['best_value']:.4f}")
+    print("Best hyperparameters:")
+    for key, value in res["best_params"].items():
+        print(f"  {key}: {value}")
+    return res
 
 
 def main(argv=None) -> None:
@@ -302,7 +461,13 @@ def main(argv=None) -> None:
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--checkpoint", default="clip_detective_best.pth")
+    ap.add_argument("--tune", action="store_true", help="run the hyperparameter study instead of one training")
+    ap.add_argument("--trials", type=int, default=10, help="number of trials of the study")
     a = ap.parse_args(argv)
+    if a.tune:
+        run_hyperparameter_tuning(n_trials=a.trials, train_csv=a.train_csv, val_csv=a.val_csv,
+                                  checkpoint_path=a.checkpoint)
+        return
     train_clip_detective(train_csv=a.train_csv, val_csv=a.val_csv, batch_size=a.batch_size, epochs=a.epochs, lr=a.lr,
                          checkpoint_path=a.checkpoint)
 

@@ -724,6 +724,62 @@ int mmf_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int 
   return 0;
 }
 
+int64_t mmf_clip_train_trials_ws_bytes(int trials, int batch_max) {
+  return (int64_t)clip_train_trials_ws_bytes(trials, batch_max);
+}
+
+namespace {
+static_assert(kClipTrialsMax == MMF_CLIP_TRIALS_MAX && kClipTrialStride == MMF_CLIP_TRIAL_STRIDE, "header and kernels");
+// the trial calls' shared checks: the trial count, N, every active trial's batch (and step0 where given), and that
+// `stride` rows of output hold every active trial's ceil(N / batch)
+int check_trials(const char* what, int N, int trials, const int32_t* batch, const int32_t* step0, const int32_t* active,
+                 int stride) {
+  if (trials < 1 || trials > MMF_CLIP_TRIALS_MAX || N < 1)
+    return fail(MMF_EINVAL, "%s: trials=%d (1..%d) N=%d (>= 1)", what, trials, MMF_CLIP_TRIALS_MAX, N);
+  for (int t = 0; t < trials; ++t) {
+    if (active && !active[t]) continue;
+    if (batch[t] < 1 || batch[t] > 64 || (step0 && step0[t] < 0))
+      return fail(MMF_EINVAL, "%s: trial %d: batch=%d (1..64) step0=%d (>= 0)", what, t, batch[t], step0 ? step0[t] : 0);
+    if ((N + batch[t] - 1) / batch[t] > stride)
+      return fail(MMF_EINVAL, "%s: trial %d has %d steps, the outputs' rows hold %d", what, t,
+                  (N + batch[t] - 1) / batch[t], stride);
+  }
+  return 0;
+}
+}  // namespace
+
+int mmf_clip_train_epoch_trials(const float* img_feat, const float* txt_feat, int N, int trials, const int32_t* perm,
+                                const int32_t* batch, const double* lr, const double* weight_decay,
+                                const double* max_norm, const int32_t* step0, const int32_t* active, double beta1,
+                                double beta2, double eps, float* params, float* exp_avg, float* exp_avg_sq,
+                                float* step_loss, float* step_gnorm, int max_nsteps, void* ws, int64_t ws_bytes,
+                                void* stream) {
+  if (!img_feat || !txt_feat || !perm || !batch || !lr || !weight_decay || !max_norm || !step0 || !params || !exp_avg ||
+      !exp_avg_sq || !step_loss || !step_gnorm || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  CHK(check_trials("clip_train_epoch_trials", N, trials, batch, step0, active, max_nsteps));
+  CHK(check_ws("clip_train_epoch_trials", ws_bytes, clip_train_trials_ws_bytes(trials, 64)));
+  CHK(check_aligned("clip_train_epoch_trials", 16, {img_feat, txt_feat, params, exp_avg, exp_avg_sq, ws}));
+  HIPCHK(launch_clip_train_epoch_trials(img_feat, txt_feat, N, trials, perm, batch, lr, weight_decay, max_norm, step0,
+                                        active, beta1, beta2, eps, params, exp_avg, exp_avg_sq, step_loss, step_gnorm,
+                                        max_nsteps, nullptr, (float*)ws, (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_clip_contrastive_eval_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                     const int32_t* batch, const int32_t* active, const float* params,
+                                     float* batch_loss, float* row_cos, int max_nb, void* ws, int64_t ws_bytes,
+                                     void* stream) {
+  if (!img_feat || !txt_feat || !batch || !params || !batch_loss || !row_cos || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  CHK(check_trials("clip_contrastive_eval_trials", N, trials, batch, nullptr, active, max_nb));
+  CHK(check_ws("clip_contrastive_eval_trials", ws_bytes, clip_train_trials_ws_bytes(trials, 64)));
+  CHK(check_aligned("clip_contrastive_eval_trials", 16, {img_feat, txt_feat, params, ws}));
+  HIPCHK(launch_clip_contrastive_eval_trials(img_feat, txt_feat, N, trials, batch, active, params, batch_loss, row_cos,
+                                             max_nb, (float*)ws, (hipStream_t)stream));
+  return 0;
+}
+
 int64_t mmf_head_train_ws_bytes(int batch) { return (int64_t)head_train_ws_bytes(batch); }
 
 int mmf_head_train_epoch(const float* feat, const int32_t* labels, int N, const int32_t* perm, const uint64_t* keep,

@@ -16,6 +16,15 @@
 // Stream order is the only synchronisation: no grid barrier, no cooperative launch, no flag, no atomics.  Every
 // reduction has a fixed order, so results are bit-reproducible and do not depend on how an epoch is split into
 // launches; the step-dependent Adam scalars are computed in double from the step number alone (as fusion_train.hip).
+//
+// Trials.  Every launch carries a trial dimension in blockIdx.z: T independent trainings (a hyperparameter study)
+// share the six launches of a step.  Per-trial state is stacked (params / moments [T][kClipTrialStride], perm [T][N],
+// one workspace image per trial, outputs [T][row stride]); a trial's batch size, step count, max_norm and that
+// step's Adam scalars travel by value in the kernel arguments (ClipTrials).  Trials differ in batch size and so in
+// steps per epoch: a workgroup whose trial has no minibatch st, or whose row lies past its trial's rows, returns at
+// its very top -- a test on blockIdx and the arguments alone, uniform over the workgroup -- and touches nothing.
+// The single-trial entry points are T = 1 through the same kernel bodies (instantiated for one trial: ClipTrials
+// below), and no workgroup reads another trial's slice, so a trial's bits do not depend on its neighbours.
 #include <algorithm>
 #include <cmath>
 
@@ -35,6 +44,7 @@ constexpr int CT_BLK = 1024;                 // elements of a wgrad / adamw bloc
 constexpr int CT_NBLK = CT_NW / CT_BLK;      // 640
 static_assert(CT_NV % CT_BLK == 0 && CT_NW % CT_BLK == 0, "a block stays inside one projection");
 static_assert(CT_NW + 1 == kClipTrainParams, "flat parameter layout");
+static_assert(kClipTrialStride >= kClipTrainParams && kClipTrialStride % 4 == 0, "a trial's slice stays 16-byte aligned");
 
 // workspace image, in floats (every region 16-byte aligned); strides are those of CT_BMAX rows whatever the batch
 constexpr size_t W_PB = 0;                                   // [2][64][768] the minibatch's feature rows
@@ -46,6 +56,28 @@ constexpr size_t W_DE = W_SC + 4;                            // [2][64][512] dL/
 constexpr size_t W_PART = W_DE + 2 * CT_BMAX * CT_D;         // [640]        per-block sums of squares
 constexpr size_t W_G = W_PART + CT_NBLK;                     // [655,360 + 4] the unclipped gradient
 constexpr size_t W_END = W_G + CT_NW + 4;
+static_assert(W_END % 4 == 0, "a trial's workspace image stays 16-byte aligned");
+
+// What a workgroup knows of its trial, by value in the kernel arguments.  nsteps: the trial's minibatches in this
+// call (0: the trial takes no part); A: the scalars of the step being launched (training only).
+struct ClipTrial {
+  int batch, nsteps;
+  float max_norm;
+  AdamScalars A;
+};
+// TM: the trials an instantiation holds.  TM = 1 (the single-trial entry points, and a study of one) knows its
+// trial at compile time, and its grids are that trial's own, so it has no idle workgroups and no test for them: it
+// reads its trial with the other arguments, as the kernels did before they had trials.  With more, a workgroup first
+// fetches t[blockIdx.z] and decides whether it has work, dependent scalar loads in front of every kernel (measured
+// through the single-trial call: 0.2 to 0.3 us per launch).
+template <int TM>
+struct ClipTrials {
+  ClipTrial t[TM];
+};
+template <int TM>
+MMF_DEV int trial_index() { return TM == 1 ? 0 : (int)blockIdx.z; }
+// rows of minibatch st of a trial, 0 where it has none
+MMF_DEV int trial_rows(const ClipTrial& t, int st, int N) { return st < t.nsteps ? min(t.batch, N - st * t.batch) : 0; }
 
 // ---- 1a. e = P W^T: grid (32 blocks of 16 outputs, 2 towers), 256 threads = 16 outputs x 16 rows ----
 // K runs in tiles of 256 staged in LDS by coalesced 16-byte loads (W rows are 2-3 KB apart: a thread walking its
@@ -54,13 +86,20 @@ constexpr size_t W_END = W_G + CT_NW + 4;
 constexpr int PJ_J = 16, PJ_R = 16, PJ_KT = 256;
 constexpr int PJ_LD = PJ_KT + 4;  // 65 x 16 bytes per row: 16 rows read as float4 fall into 16 different bank groups
 static_assert(CT_KV % PJ_KT == 0 && CT_KT % PJ_KT == 0 && CT_D % PJ_J == 0, "projection tiles");
+// grid z: the trial (its perm row, parameter slice and workspace image)
+template <int TM>
 __global__ __launch_bounds__(256) void clip_project_kernel(const float* img_feat, const float* txt_feat, int N,
-                                                           const int32_t* perm, int pos0, int rows,
+                                                           const int32_t* perm, int st, ClipTrials<TM> T,
                                                            const float* params, float* ws) {
+  const int z = trial_index<TM>(), rows = trial_rows(T.t[z], st, N);
+  if (TM > 1 && rows == 0) return;
   __shared__ __attribute__((aligned(16))) float Ws[PJ_J * PJ_LD], Ps[PJ_R * PJ_LD];
   __shared__ int srcs[CT_BMAX];
   const int jb = blockIdx.x, tw = blockIdx.y, tid = threadIdx.x;
-  const int K = tw ? CT_KT : CT_KV;
+  const int K = tw ? CT_KT : CT_KV, pos0 = st * T.t[z].batch;
+  if (perm) perm += (size_t)z * N;
+  params += (size_t)z * kClipTrialStride;
+  ws += (size_t)z * W_END;
   if (tid < rows) srcs[tid] = perm ? min(max(perm[pos0 + tid], 0), N - 1) : pos0 + tid;
   __syncthreads();
   const float* feat = tw ? txt_feat : img_feat;
@@ -102,9 +141,13 @@ __global__ __launch_bounds__(256) void clip_project_kernel(const float* img_feat
 }
 
 // ---- 1b. the row norm (a fixed tree over 512 squares) and e / norm, in place: grid (rows, 2), 256 threads ----
-__global__ __launch_bounds__(256) void clip_normalise_kernel(float* ws) {
+template <int TM>
+__global__ __launch_bounds__(256) void clip_normalise_kernel(int N, int st, ClipTrials<TM> T, float* ws) {
+  const int z = trial_index<TM>();
+  if (TM > 1 && (int)blockIdx.x >= trial_rows(T.t[z], st, N)) return;
   __shared__ float red[256];
   const int r = blockIdx.x, tw = blockIdx.y, tid = threadIdx.x;
+  ws += (size_t)z * W_END;
   float* eh = ws + W_EH + ((size_t)tw * CT_BMAX + r) * CT_D;
   const float e0 = eh[tid], e1 = eh[tid + 256];
   const float nrm = sqrtf(block_tree_sum(fmaf(e1, e1, e0 * e0), red, tid));
@@ -131,10 +174,17 @@ MMF_DEV float dot512(const float* a, const float* b) {
   return s;
 }
 
-// ---- 2. logits, both softmaxes, loss, dL/dlogits, dL/dlogit_scale: ONE workgroup of 256 threads ----
-// train: D and the scalars go to the workspace; else row_cos[i] = cos[i][i]
-__global__ __launch_bounds__(256) void clip_logits_kernel(int rows, const float* params, float* ws, float* loss_out,
-                                                          float* row_cos, int train) {
+// ---- 2. logits, both softmaxes, loss, dL/dlogits, dL/dlogit_scale: ONE workgroup of 256 threads per trial ----
+// train: D and the scalars go to the workspace; else row_cos[i] = cos[i][i] (row_cos [T][N]).  loss_out [T][ostride].
+template <int TM>
+__global__ __launch_bounds__(256) void clip_logits_kernel(int N, int st, ClipTrials<TM> T, const float* params, float* ws,
+                                                          float* loss_out, int ostride, float* row_cos, int train) {
+  const int z = trial_index<TM>(), rows = trial_rows(T.t[z], st, N);
+  if (TM > 1 && rows == 0) return;
+  params += (size_t)z * kClipTrialStride;
+  ws += (size_t)z * W_END;
+  loss_out += (size_t)z * ostride + st;
+  if (!train) row_cos += (size_t)z * N + (size_t)st * T.t[z].batch;
   __shared__ float L[CT_BMAX * CT_BMAX];        // logits [i][j] (image row i, text row j)
   __shared__ float DL[CT_BMAX * CT_BMAX];       // dL/dlogits
   __shared__ float mx[2 * CT_BMAX], sm[2 * CT_BMAX], part[CT_BMAX];
@@ -152,11 +202,11 @@ __global__ __launch_bounds__(256) void clip_logits_kernel(int rows, const float*
   // thread t < B: the softmax of image row t over the texts; B <= t < 2B: of text row t - B over the images
   if (tid < 2 * B) {
     const int r = tid < B ? tid : tid - B;
-    const int st = tid < B ? 1 : CT_BMAX, base = tid < B ? r * CT_BMAX : r;
+    const int ld = tid < B ? 1 : CT_BMAX, base = tid < B ? r * CT_BMAX : r;
     float m = L[base];
-    for (int q = 1; q < B; ++q) m = fmaxf(m, L[base + q * st]);
+    for (int q = 1; q < B; ++q) m = fmaxf(m, L[base + q * ld]);
     float s = 0.f;
-    for (int q = 0; q < B; ++q) s += expf(L[base + q * st] - m);
+    for (int q = 0; q < B; ++q) s += expf(L[base + q * ld] - m);
     mx[tid] = m;
     sm[tid] = s;
   }
@@ -200,7 +250,11 @@ __global__ __launch_bounds__(256) void clip_logits_kernel(int rows, const float*
 }
 
 // ---- 3. dL/de of one row: grid (rows, 2), 128 threads (4 columns each) ----
-__global__ __launch_bounds__(128) void clip_embgrad_kernel(int rows, float* ws) {
+template <int TM>
+__global__ __launch_bounds__(128) void clip_embgrad_kernel(int N, int st, ClipTrials<TM> T, float* ws) {
+  const int z = trial_index<TM>(), rows = trial_rows(T.t[z], st, N);
+  if (TM > 1 && (int)blockIdx.x >= rows) return;
+  ws += (size_t)z * W_END;
   __shared__ float coef[CT_BMAX];
   __shared__ __attribute__((aligned(16))) float dy[CT_D], y[CT_D];
   __shared__ float dots;
@@ -250,7 +304,11 @@ __global__ __launch_bounds__(128) void clip_embgrad_kernel(int rows, float* ws) 
 }
 
 // ---- 4. dW[j][k] = sum_r de[r][j] P[r][k]: 640 blocks of 256 threads, 4 consecutive k per thread ----
-__global__ __launch_bounds__(256) void clip_wgrad_kernel(int rows, float* ws) {
+template <int TM>
+__global__ __launch_bounds__(256) void clip_wgrad_kernel(int N, int st, ClipTrials<TM> T, float* ws) {
+  const int z = trial_index<TM>(), rows = trial_rows(T.t[z], st, N);
+  if (TM > 1 && rows == 0) return;
+  ws += (size_t)z * W_END;
   __shared__ float red[256];
   const int tid = threadIdx.x;
   const int flat = blockIdx.x * CT_BLK + tid * 4;
@@ -287,9 +345,21 @@ __global__ __launch_bounds__(256) void clip_wgrad_kernel(int rows, float* ws) {
 }
 
 // ---- 5. total norm, clip coefficient, AdamW: 640 blocks of 256 threads ----
-__global__ __launch_bounds__(256) void clip_adamw_kernel(AdamScalars A, float max_norm, float* params, float* exp_avg,
+// gnorm_out [T][ostride]; grad_out (the single-trial call's, else NULL): trial 0's clipped gradient
+template <int TM>
+__global__ __launch_bounds__(256) void clip_adamw_kernel(int st, ClipTrials<TM> T, float* params, float* exp_avg,
                                                          float* exp_avg_sq, const float* ws, float* gnorm_out,
-                                                         float* grad_out) {
+                                                         int ostride, float* grad_out) {
+  const int z = trial_index<TM>();
+  if (TM > 1 && st >= T.t[z].nsteps) return;
+  const AdamScalars A = T.t[z].A;
+  const float max_norm = T.t[z].max_norm;
+  params += (size_t)z * kClipTrialStride;
+  exp_avg += (size_t)z * kClipTrialStride;
+  exp_avg_sq += (size_t)z * kClipTrialStride;
+  ws += (size_t)z * W_END;
+  gnorm_out += (size_t)z * ostride + st;
+  if (z) grad_out = nullptr;
   __shared__ float red[256];
   const int tid = threadIdx.x;
   const int flat = blockIdx.x * CT_BLK + tid * 4;
@@ -336,46 +406,124 @@ __global__ __launch_bounds__(256) void f32_to_f16_kernel(const float* src, f16_t
 }  // namespace
 
 size_t clip_train_ws_bytes(int batch) { return (batch < 1 || batch > CT_BMAX) ? 0 : W_END * sizeof(float); }
+size_t clip_train_trials_ws_bytes(int trials, int batch_max) {
+  return (trials < 1 || trials > kClipTrialsMax) ? 0 : (size_t)trials * clip_train_ws_bytes(batch_max);
+}
 
-hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, const int32_t* perm, int batch,
-                                   double lr, double beta1, double beta2, double eps, double weight_decay,
-                                   double max_norm, int step0, float* params, float* exp_avg, float* exp_avg_sq,
-                                   float* step_loss, float* step_gnorm, float* grad_out, float* ws, hipStream_t s) {
-  if (N < 1 || batch < 1 || batch > CT_BMAX) return hipErrorInvalidValue;
-  const int nsteps = (N + batch - 1) / batch;
-  for (int st = 0; st < nsteps; ++st) {
-    const int pos0 = st * batch, rows = std::min(batch, N - pos0);
-    const AdamScalars A = adam_scalars(lr, beta1, beta2, eps, weight_decay, step0 + st + 1);
-    hipLaunchKernelGGL(clip_project_kernel, dim3(CT_D / PJ_J, 2), dim3(256), 0, s, img_feat, txt_feat, N, perm, pos0,
-                       rows, params, ws);
-    hipLaunchKernelGGL(clip_normalise_kernel, dim3(rows, 2), dim3(256), 0, s, ws);
-    hipLaunchKernelGGL(clip_logits_kernel, dim3(1), dim3(256), 0, s, rows, params, ws, step_loss + st, nullptr, 1);
-    hipLaunchKernelGGL(clip_embgrad_kernel, dim3(rows, 2), dim3(128), 0, s, rows, ws);
-    hipLaunchKernelGGL(clip_wgrad_kernel, dim3(CT_NBLK), dim3(256), 0, s, rows, ws);
-    hipLaunchKernelGGL(clip_adamw_kernel, dim3(CT_NBLK), dim3(256), 0, s, A, (float)max_norm, params, exp_avg,
-                       exp_avg_sq, ws, step_gnorm + st, st == nsteps - 1 ? grad_out : nullptr);
+namespace {
+// The trials' step counts for N rows (0 for a trial that is not active; active NULL: all are) into T; the largest
+// of them, or -1 on a trial count, N or an active trial's batch out of range.
+template <int TM>
+int plan_trials(int N, int trials, const int32_t* batch, const int32_t* active, ClipTrials<TM>& T) {
+  if (N < 1 || trials < 1 || trials > TM) return -1;
+  T = ClipTrials<TM>{};
+  int most = 0;
+  for (int t = 0; t < trials; ++t) {
+    if (active && !active[t]) continue;
+    if (batch[t] < 1 || batch[t] > CT_BMAX) return -1;
+    T.t[t].batch = batch[t];
+    T.t[t].nsteps = (N + batch[t] - 1) / batch[t];
+    most = std::max(most, T.t[t].nsteps);
+  }
+  return most;
+}
+// the largest minibatch st among the trials that have one: what the row grids are sized by
+template <int TM>
+int most_rows(const ClipTrials<TM>& T, int trials, int st, int N) {
+  int rows = 0;
+  for (int t = 0; t < trials; ++t)
+    if (st < T.t[t].nsteps) rows = std::max(rows, std::min(T.t[t].batch, N - st * T.t[t].batch));
+  return rows;
+}
+
+template <int TM>
+hipError_t train_epoch_trials(const float* img_feat, const float* txt_feat, int N, int trials, const int32_t* perm,
+                              const int32_t* batch, const double* lr, const double* weight_decay,
+                              const double* max_norm, const int32_t* step0, const int32_t* active, double beta1,
+                              double beta2, double eps, float* params, float* exp_avg, float* exp_avg_sq,
+                              float* step_loss, float* step_gnorm, int max_nsteps, float* grad_out, float* ws,
+                              hipStream_t s) {
+  ClipTrials<TM> T;
+  const int most = plan_trials(N, trials, batch, active, T);
+  if (most < 0 || most > max_nsteps) return hipErrorInvalidValue;
+  for (int t = 0; t < trials; ++t) T.t[t].max_norm = (float)max_norm[t];
+  for (int st = 0; st < most; ++st) {
+    for (int t = 0; t < trials; ++t)
+      if (st < T.t[t].nsteps) T.t[t].A = adam_scalars(lr[t], beta1, beta2, eps, weight_decay[t], step0[t] + st + 1);
+    const int rows = most_rows(T, trials, st, N);
+    hipLaunchKernelGGL(clip_project_kernel<TM>, dim3(CT_D / PJ_J, 2, trials), dim3(256), 0, s, img_feat, txt_feat, N,
+                       perm, st, T, params, ws);
+    hipLaunchKernelGGL(clip_normalise_kernel<TM>, dim3(rows, 2, trials), dim3(256), 0, s, N, st, T, ws);
+    hipLaunchKernelGGL(clip_logits_kernel<TM>, dim3(1, 1, trials), dim3(256), 0, s, N, st, T, params, ws, step_loss,
+                       max_nsteps, nullptr, 1);
+    hipLaunchKernelGGL(clip_embgrad_kernel<TM>, dim3(rows, 2, trials), dim3(128), 0, s, N, st, T, ws);
+    hipLaunchKernelGGL(clip_wgrad_kernel<TM>, dim3(CT_NBLK, 1, trials), dim3(256), 0, s, N, st, T, ws);
+    hipLaunchKernelGGL(clip_adamw_kernel<TM>, dim3(CT_NBLK, 1, trials), dim3(256), 0, s, st, T, params, exp_avg,
+                       exp_avg_sq, ws, step_gnorm, max_nsteps, st == most - 1 ? grad_out : nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-hipError_t launch_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch,
-                                        const float* params, float* batch_loss, float* row_cos, float* ws,
-                                        hipStream_t s) {
-  if (N < 1 || batch < 1 || batch > CT_BMAX) return hipErrorInvalidValue;
-  const int nb = (N + batch - 1) / batch;
-  for (int b = 0; b < nb; ++b) {
-    const int pos0 = b * batch, rows = std::min(batch, N - pos0);
-    hipLaunchKernelGGL(clip_project_kernel, dim3(CT_D / PJ_J, 2), dim3(256), 0, s, img_feat, txt_feat, N, nullptr, pos0,
-                       rows, params, ws);
-    hipLaunchKernelGGL(clip_normalise_kernel, dim3(rows, 2), dim3(256), 0, s, ws);
-    hipLaunchKernelGGL(clip_logits_kernel, dim3(1), dim3(256), 0, s, rows, params, ws, batch_loss + b, row_cos + pos0,
-                       0);
+template <int TM>
+hipError_t contrastive_eval_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                   const int32_t* batch, const int32_t* active, const float* params, float* batch_loss,
+                                   float* row_cos, int max_nb, float* ws, hipStream_t s) {
+  ClipTrials<TM> T;
+  const int most = plan_trials(N, trials, batch, active, T);
+  if (most < 0 || most > max_nb) return hipErrorInvalidValue;
+  for (int b = 0; b < most; ++b) {
+    hipLaunchKernelGGL(clip_project_kernel<TM>, dim3(CT_D / PJ_J, 2, trials), dim3(256), 0, s, img_feat, txt_feat, N,
+                       (const int32_t*)nullptr, b, T, params, ws);
+    hipLaunchKernelGGL(clip_normalise_kernel<TM>, dim3(most_rows(T, trials, b, N), 2, trials), dim3(256), 0, s, N, b, T,
+                       ws);
+    hipLaunchKernelGGL(clip_logits_kernel<TM>, dim3(1, 1, trials), dim3(256), 0, s, N, b, T, params, ws, batch_loss,
+                       max_nb, row_cos, 0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+}  // namespace
+
+hipError_t launch_clip_train_epoch_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                          const int32_t* perm, const int32_t* batch, const double* lr,
+                                          const double* weight_decay, const double* max_norm, const int32_t* step0,
+                                          const int32_t* active, double beta1, double beta2, double eps, float* params,
+                                          float* exp_avg, float* exp_avg_sq, float* step_loss, float* step_gnorm,
+                                          int max_nsteps, float* grad_out, float* ws, hipStream_t s) {
+  const auto run = trials == 1 ? train_epoch_trials<1> : train_epoch_trials<kClipTrialsMax>;
+  return run(img_feat, txt_feat, N, trials, perm, batch, lr, weight_decay, max_norm, step0, active, beta1, beta2, eps,
+             params, exp_avg, exp_avg_sq, step_loss, step_gnorm, max_nsteps, grad_out, ws, s);
+}
+
+hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat, int N, const int32_t* perm, int batch,
+                                   double lr, double beta1, double beta2, double eps, double weight_decay,
+                                   double max_norm, int step0, float* params, float* exp_avg, float* exp_avg_sq,
+                                   float* step_loss, float* step_gnorm, float* grad_out, float* ws, hipStream_t s) {
+  if (N < 1 || batch < 1 || batch > CT_BMAX) return hipErrorInvalidValue;
+  const int32_t b = batch, s0 = step0;
+  return launch_clip_train_epoch_trials(img_feat, txt_feat, N, 1, perm, &b, &lr, &weight_decay, &max_norm, &s0, nullptr,
+                                        beta1, beta2, eps, params, exp_avg, exp_avg_sq, step_loss, step_gnorm,
+                                        (N + batch - 1) / batch, grad_out, ws, s);
+}
+
+hipError_t launch_clip_contrastive_eval_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                               const int32_t* batch, const int32_t* active, const float* params,
+                                               float* batch_loss, float* row_cos, int max_nb, float* ws,
+                                               hipStream_t s) {
+  const auto run = trials == 1 ? contrastive_eval_trials<1> : contrastive_eval_trials<kClipTrialsMax>;
+  return run(img_feat, txt_feat, N, trials, batch, active, params, batch_loss, row_cos, max_nb, ws, s);
+}
+
+hipError_t launch_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch,
+                                        const float* params, float* batch_loss, float* row_cos, float* ws,
+                                        hipStream_t s) {
+  if (N < 1 || batch < 1 || batch > CT_BMAX) return hipErrorInvalidValue;
+  const int32_t b = batch;
+  return launch_clip_contrastive_eval_trials(img_feat, txt_feat, N, 1, &b, nullptr, params, batch_loss, row_cos,
+                                             (N + batch - 1) / batch, ws, s);
 }
 
 hipError_t launch_f32_to_f16(const float* src, f16_t* dst, size_t n, hipStream_t s) {

@@ -172,6 +172,27 @@ hipError_t launch_clip_train_epoch(const float* img_feat, const float* txt_feat,
 hipError_t launch_clip_contrastive_eval(const float* img_feat, const float* txt_feat, int N, int batch,
                                         const float* params, float* batch_loss, float* row_cos, float* ws,
                                         hipStream_t s);
+// The same for `trials` independent trainings side by side in the same launches (include/mmf_hip.h
+// mmf_clip_train_epoch_trials / mmf_clip_contrastive_eval_trials): params / exp_avg / exp_avg_sq
+// [trials][kClipTrialStride], perm [trials][N], step_loss / step_gnorm [trials][max_nsteps], batch_loss
+// [trials][max_nb], row_cos [trials][N], ws of clip_train_trials_ws_bytes(trials, 64) bytes (0 for trials outside
+// 1..kClipTrialsMax).  batch, lr, weight_decay, max_norm, step0, active are HOST arrays [trials] read at enqueue time
+// (active NULL: every trial).  grad_out (NULL but for the single-trial call): trial 0's last clipped gradient.
+// hipErrorInvalidValue with nothing launched: trials, N or an active trial's batch out of range, max_nsteps /
+// max_nb below an active trial's step count.
+constexpr int kClipTrialsMax = 16;
+constexpr int kClipTrialStride = 655364;  // kClipTrainParams rounded up to 4 floats: every slice 16-byte aligned
+size_t clip_train_trials_ws_bytes(int trials, int batch_max);
+hipError_t launch_clip_train_epoch_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                          const int32_t* perm, const int32_t* batch, const double* lr,
+                                          const double* weight_decay, const double* max_norm, const int32_t* step0,
+                                          const int32_t* active, double beta1, double beta2, double eps, float* params,
+                                          float* exp_avg, float* exp_avg_sq, float* step_loss, float* step_gnorm,
+                                          int max_nsteps, float* grad_out, float* ws, hipStream_t s);
+hipError_t launch_clip_contrastive_eval_trials(const float* img_feat, const float* txt_feat, int N, int trials,
+                                               const int32_t* batch, const int32_t* active, const float* params,
+                                               float* batch_loss, float* row_cos, int max_nb, float* ws,
+                                               hipStream_t s);
 // a RoBERTa text head (Linear(768,256)-ReLU-Dropout-Linear(256,2)) on cached CLS rows (head_train.hip;
 // include/mmf_hip.h mmf_head_train_epoch / mmf_head_eval): four launches per minibatch (two for the eval), ws of
 // head_train_ws_bytes(batch) bytes (0 for a batch outside 1..64); lr_steps is a HOST array read at enqueue time;

@@ -626,6 +626,65 @@ class Engine:
               "mmf_clip_contrastive_eval")
         return batch_loss, row_cos
 
+    CLIP_TRIALS_MAX, CLIP_TRIAL_STRIDE = 16, 655364  # MMF_CLIP_TRIALS_MAX, MMF_CLIP_TRIAL_STRIDE
+
+    def _trial_args(self, what: str, T: int, N: int, batch, active):
+        """The host arrays of a trials call: (batch int32 [T], active int32 [T], the largest active step count)."""
+        if not 1 <= T <= self.CLIP_TRIALS_MAX:
+            raise ValueError(f"{what}: {T} trials, 1..{self.CLIP_TRIALS_MAX} fit one call")
+        b = np.ascontiguousarray(np.asarray(batch, dtype=np.int32).reshape(-1))
+        a = np.ones(T, np.int32) if active is None else np.ascontiguousarray(
+            (np.asarray(active).reshape(-1) != 0).astype(np.int32))
+        if b.shape != (T,) or a.shape != (T,):
+            raise ValueError(f"{what}: batch and active must have {T} entries")
+        most = max([self._nsteps(N, int(b[t])) for t in range(T) if a[t]], default=1)
+        return b, a, most
+
+    def clip_train_epoch_trials(self, img_feat, txt_feat, perm, batch, lr, betas, eps: float, weight_decay, max_norm,
+                                step0, params, exp_avg, exp_avg_sq, active=None):
+        """One epoch of T projection-head trainings side by side (mmf_clip_train_epoch_trials): img_feat /
+        txt_feat as clip_train_epoch's, shared; perm int32 [T, N]; params / exp_avg / exp_avg_sq float32
+        [T, 655364] (a trial's 655361 values first), updated in place; batch, lr, weight_decay, max_norm, step0,
+        active: T host values each (active None: all).  Returns (step_loss, step_gnorm) float32 [T, S] on the
+        device, S the largest active step count; a trial's row is NaN past its own steps, and all NaN when it is
+        not active.  Nothing is synchronised."""
+        T, N, S = int(params.shape[0]), int(img_feat.shape[0]), self.CLIP_TRIAL_STRIDE
+        self._check_tensors("clip_train_epoch_trials", (
+            ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
+            ("perm", perm, torch.int32, T * N, False), ("params", params, torch.float32, T * S, False),
+            ("exp_avg", exp_avg, torch.float32, T * S, False), ("exp_avg_sq", exp_avg_sq, torch.float32, T * S, False)))
+        b, a, most = self._trial_args("clip_train_epoch_trials", T, N, batch, active)
+        f64 = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (lr, weight_decay, max_norm)]
+        s0 = np.ascontiguousarray(np.asarray(step0, dtype=np.int32).reshape(-1))
+        if any(x.shape != (T,) for x in f64 + [s0]):
+            raise ValueError(f"clip_train_epoch_trials: lr, weight_decay, max_norm and step0 must have {T} entries")
+        step_loss = torch.full((T, most), float("nan"), dtype=torch.float32, device=self.device)
+        step_gnorm = torch.full_like(step_loss, float("nan"))
+        ws = self._workspace("clip_train", self.lib.mmf_clip_train_trials_ws_bytes(T, 64))
+        check(self.lib.mmf_clip_train_epoch_trials(
+            ptr(img_feat), ptr(txt_feat), N, T, ptr(perm), b.ctypes.data, f64[0].ctypes.data, f64[1].ctypes.data,
+            f64[2].ctypes.data, s0.ctypes.data, a.ctypes.data, float(betas[0]), float(betas[1]), float(eps),
+            ptr(params), ptr(exp_avg), ptr(exp_avg_sq), ptr(step_loss), ptr(step_gnorm), most, ptr(ws), ws.numel(),
+            stream_ptr()), "mmf_clip_train_epoch_trials")
+        return step_loss, step_gnorm
+
+    def clip_contrastive_eval_trials(self, img_feat, txt_feat, batch, params, active=None):
+        """validate's forward for T trials side by side (mmf_clip_contrastive_eval_trials): params float32
+        [T, 655364]; batch, active: T host values each -> (batch_loss float32 [T, S], row_cos float32 [T, N]) on
+        the device, S the largest active batch count; NaN where a trial wrote nothing."""
+        T, N = int(params.shape[0]), int(img_feat.shape[0])
+        self._check_tensors("clip_contrastive_eval_trials", (
+            ("img_feat", img_feat, torch.float32, 768 * N, False), ("txt_feat", txt_feat, torch.float32, 512 * N, False),
+            ("params", params, torch.float32, T * self.CLIP_TRIAL_STRIDE, False)))
+        b, a, most = self._trial_args("clip_contrastive_eval_trials", T, N, batch, active)
+        batch_loss = torch.full((T, most), float("nan"), dtype=torch.float32, device=self.device)
+        row_cos = torch.full((T, N), float("nan"), dtype=torch.float32, device=self.device)
+        ws = self._workspace("clip_train", self.lib.mmf_clip_train_trials_ws_bytes(T, 64))
+        check(self.lib.mmf_clip_contrastive_eval_trials(
+            ptr(img_feat), ptr(txt_feat), N, T, b.ctypes.data, a.ctypes.data, ptr(params), ptr(batch_loss),
+            ptr(row_cos), most, ptr(ws), ws.numel(), stream_ptr()), "mmf_clip_contrastive_eval_trials")
+        return batch_loss, row_cos
+
     HEAD_PARAMS = 197378  # MMF_HEAD_PARAMS: 0.weight [256][768] | 0.bias [256] | 3.weight [2][256] | 3.bias [2]
 
     def head_train_epoch(self, feat, labels, perm, keep, p_drop: float, batch: int, lr_steps, betas, eps: float,

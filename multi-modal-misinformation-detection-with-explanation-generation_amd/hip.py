@@ -46,6 +46,10 @@ SIGNATURES = {
     "mmf_clip_train_epoch": (_I, [_P, _P, _I, _P, _I, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P,
                                   ctypes.c_int64, _P]),
     "mmf_clip_contrastive_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "mmf_clip_train_trials_ws_bytes": (ctypes.c_int64, [_I, _I]),
+    "mmf_clip_train_epoch_trials": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _P, _I,
+                                         _P, ctypes.c_int64, _P]),
+    "mmf_clip_contrastive_eval_trials": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, ctypes.c_int64, _P]),
     "mmf_resize_pil": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mmf_resize_supported": (_I, [_I, _I]),
     "mmf_jpeg_header": (_I, [_P, ctypes.c_int64, _P]),

@@ -10,6 +10,13 @@ Prints one JSON object:
            (autocast + GradScaler + clip_grad_norm_ + AdamW + loss.item(); host clock around a loop that ends in a
            synchronise), both after a warm-up epoch: the step-only comparison.  `eval_us_per_batch`: the validation
            call.
+  tune     the study's launches (mmf_clip_train_epoch_trials): microseconds per step-of-all-trials at batch 16 on the
+           same cached rows for T = 1, 4, 10 and 16 concurrent trials, against T sequential single-trial epochs
+           through mmf_clip_train_epoch in the same process, both by device events after a warm-up epoch,
+           interleaved over three rounds (`*_us_per_step`: the rounds; `ratio`: sequential / concurrent of the
+           medians; `spread`: (max - min) / median of the rounds, the larger of the two sides).  `mixed`: one group
+           of nine trials with batch sizes 8 / 12 / 16 (256 steps, the 12s and 16s finishing early) per epoch,
+           against the nine epochs one after another.
   towers   what the reference does in addition per minibatch -- both 12-layer towers forward on 16 rows -- as
            this package's own HIP towers take for it (clip_pooled at batch 16, device events): the part of a step
            that caching the features removes.  The reference's torch towers are not timed here.
@@ -140,6 +147,74 @@ def bench_train(mf, n_rows, epochs, batch=16, lr=1e-4):
             "torch_last_epoch_loss": round(last, 4)}
 
 
+def bench_tune(mf, n_rows, batch=16, rounds=3, reps=10, lr=1e-4):
+    import mmf_amd.clip_training as CT
+    eng, dev = mf.engine, mf.engine.device
+    g = np.random.default_rng(7)
+    img = g.standard_normal((n_rows, 768)).astype(np.float32)
+    txt = (0.7 * g.standard_normal((n_rows, 512)) + 0.7 * img[:, :512]).astype(np.float32)
+    ti, tt = torch.from_numpy(img).to(dev), torch.from_numpy(txt).to(dev)
+    TM = CT.TRIALS_MAX
+    start = CT.flatten_heads(mf.clip_state).to(dev)
+    perms = torch.stack([torch.randperm(n_rows, generator=torch.Generator().manual_seed(t)).to(torch.int32)
+                         for t in range(TM)]).to(dev)
+    lrs = [lr * (1 + 0.1 * t) for t in range(TM)]
+
+    def fresh():
+        p = torch.zeros(TM, CT.TRIAL_STRIDE, dtype=torch.float32, device=dev)
+        p[:, :CT.N_PARAMS] = start
+        return p, torch.zeros_like(p), torch.zeros_like(p)
+
+    def timed(fn):
+        ev = _events()
+        ev[0].record()
+        for _ in range(reps):
+            out = fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        assert not any(torch.isinf(o).any() for o in out)  # (NaN: the padding of a trial with fewer steps)
+        return 1e3 * ev[0].elapsed_time(ev[1]) / reps  # microseconds per epoch of all trials
+
+    def concurrent(state, bs):
+        T = len(bs)
+        p, m, v = (x[:T] for x in state)
+        return lambda: eng.clip_train_epoch_trials(ti, tt, perms[:T], bs, lrs[:T], CT.BETAS, CT.EPS, [0.01] * T,
+                                                   [1.0] * T, [0] * T, p, m, v)
+
+    def sequential(state, bs):
+        p, m, v = state
+
+        def run():
+            for t, b in enumerate(bs):
+                out = eng.clip_train_epoch(ti, tt, perms[t], b, lrs[t], CT.BETAS, CT.EPS, 0.01, 1.0, 0,
+                                           p[t, :CT.N_PARAMS], m[t, :CT.N_PARAMS], v[t, :CT.N_PARAMS])
+            return out
+        return run
+
+    groups = {f"T{T}": [batch] * T for T in (1, 4, 10, 16)}
+    groups["mixed"] = [8, 12, 16] * 3
+    runs = {k: (concurrent(fresh(), bs), sequential(fresh(), bs)) for k, bs in groups.items()}
+    for con, seq in runs.values():  # the warm-up epoch of every group, both ways
+        con()
+        seq()
+    torch.cuda.synchronize()
+    times = {k: ([], []) for k in groups}
+    for _ in range(rounds):
+        for k, (con, seq) in runs.items():
+            times[k][0].append(timed(con))
+            times[k][1].append(timed(seq))
+    out = {"rows": n_rows, "batch": batch, "rounds": rounds, "epochs_per_timing": reps}
+    for k, bs in groups.items():
+        steps = max(-(-n_rows // b) for b in bs)
+        con, seq = (np.array(x) for x in times[k])
+        spread = max(float((x.max() - x.min()) / np.median(x)) for x in (con, seq))
+        out[k] = {"trials": len(bs), "batch_sizes": sorted(set(bs)), "steps_of_all_trials": steps,
+                  "concurrent_us_per_step": [round(float(x) / steps, 2) for x in con],
+                  "sequential_us_per_step": [round(float(x) / steps, 2) for x in seq],
+                  "ratio": round(float(np.median(seq) / np.median(con)), 3), "spread": round(spread, 4)}
+    return out
+
+
 def bench_towers(mf, batch=16, reps=20):
     import mmf_amd.synthetic as syn
     eng = mf.engine
@@ -188,8 +263,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("clip_train_bench needs a HIP device")
     mf, texts = _forensics(a.rows)
-    res = {"train": bench_train(mf, a.train_rows, a.epochs), "towers": bench_towers(mf),
-           "extract": bench_extract(mf, texts, a.rows)}
+    res = {"train": bench_train(mf, a.train_rows, a.epochs), "tune": bench_tune(mf, a.train_rows),
+           "towers": bench_towers(mf), "extract": bench_extract(mf, texts, a.rows)}
     mf.engine.close()
     line = json.dumps(res)
     print(line)
