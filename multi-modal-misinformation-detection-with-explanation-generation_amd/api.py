@@ -28,6 +28,7 @@ import xxhash
 from . import explain, io_utils, weights as W
 from .engine import Engine, NO_INPUT_ERROR, SCORE_KEYS
 from .hip import MMFError
+from .precision import rerun_if
 
 _DEFAULT_CLIP_DIR = r"C:\Users\Lenovo\OneDrive\Desktop\hack\models\clip-vit-b32"
 
@@ -499,20 +500,17 @@ class MisinfoForensics:
         """misinfo_forensics.py:319-352."""
         ids = self._rob_ids(text)
         self.detector.sync(("text",))
-        _, _, sc = self.engine.text_forward(ids, np.ones_like(ids))
-        s = sc.cpu().numpy()
-        if self.engine.text_overflow(s):  # fp16 branch output overflowed: re-run in the precise mode
-            s = self.engine.text_forward(ids, np.ones_like(ids))[2].cpu().numpy()
+        # (an overflowed fp16 branch output: once more in the precise mode)
+        s = rerun_if(self.engine.text_overflow,
+                     lambda: self.engine.text_forward(ids, np.ones_like(ids))[2].cpu().numpy())
         return {"ai_score": float(s[0, 0]), "misinfo_score": float(s[0, 1])}
 
     def analyze_image(self, image_path) -> Dict[str, float]:
         """misinfo_forensics.py:354-373."""
         px = io_utils.effnet_pixels(io_utils.to_pil(image_path))[None]
         self.detector.sync(("effnet",))
-        _, sc = self.engine.effnet_forward(px)
-        s = sc.cpu().numpy()
-        if self.engine.effnet_overflow(s):  # fp16 activation overflowed: re-run on the fp32 tower
-            s = self.engine.effnet_forward(px)[1].cpu().numpy()
+        # (an overflowed fp16 activation: once more on the fp32 tower)
+        s = rerun_if(self.engine.effnet_overflow, lambda: self.engine.effnet_forward(px)[1].cpu().numpy())
         return {"deepfake_score": float(s[0])}
 
     def _image_emb(self, pil, check: bool = True) -> torch.Tensor:
@@ -527,9 +525,10 @@ class MisinfoForensics:
         key = xxhash.xxh3_128_digest(px.tobytes()) if self.reuse_image_embedding else None
         if key is not None and self._emb_cache is not None and self._emb_cache[0] == key:
             return self._emb_cache[1]
-        emb = self.engine.clip_image(px[None])
-        if check and self.engine.clip_stream_overflow(emb):  # fp16 stream overflow: re-run on fp32 streams
-            emb = self.engine.clip_image(px[None])
+
+        def run():
+            return self.engine.clip_image(px[None])
+        emb = rerun_if(self.engine.clip_stream_overflow, run) if check else run()  # (once more on fp32 streams)
         self._emb_cache = (key, emb)
         self.vit_passes += 1
         return emb
@@ -542,7 +541,8 @@ class MisinfoForensics:
         i = self._image_emb(pil, check=False)
         sim = float((t * i).sum().item())
         # the cosine is non-finite iff either embedding overflowed an fp16 stream: checked on the value
-        # read back anyway (no isfinite launches); then both are re-run on fp32 streams
+        # read back anyway (no isfinite launches); then both are re-run on fp32 streams.  (Not rerun_if: the
+        # re-run differs from the first run -- it drops the cached embedding and checks the new one itself)
         if not math.isfinite(sim) and self.engine.clip_stream_overflow(np.array([sim])):
             self._emb_cache = None
             t = self.engine.clip_text(ids, mask)
@@ -558,9 +558,7 @@ class MisinfoForensics:
         temb = None
         if user_caption:
             ids, mask = self._clip_ids([user_caption], truncation=True)
-            temb = self.engine.clip_text(ids, mask)
-            if self.engine.clip_stream_overflow(temb):
-                temb = self.engine.clip_text(ids, mask)
+            temb = rerun_if(self.engine.clip_stream_overflow, lambda: self.engine.clip_text(ids, mask))
         k = len(range(len(self.vault_metadata))[-top_k:])  # np.argsort(s)[-top_k:] keeps this many rows
         if k == 0:
             raise IndexError("index 0 is out of bounds for axis 0 with size 0")  # top_similarities[0]
@@ -598,20 +596,22 @@ class MisinfoForensics:
         F = len(pils)
         self.detector.sync(("effnet",))
         cap = self.engine.max_batch  # frames beyond the reserved batch run as further launches
-        dsc = torch.cat([self.engine.effnet_forward(eff[i:i + cap])[1] for i in range(0, F, cap)])
-        if self.engine.effnet_overflow(dsc.cpu().numpy()):
-            dsc = torch.cat([self.engine.effnet_forward(eff[i:i + cap])[1] for i in range(0, F, cap)])
-        iemb = torch.cat([self.engine.clip_image(clp[i:i + cap]) for i in range(0, F, cap)])
-        if self.engine.clip_stream_overflow(iemb):
-            iemb = torch.cat([self.engine.clip_image(clp[i:i + cap]) for i in range(0, F, cap)])
+
+        def deepfake_scores():
+            return torch.cat([self.engine.effnet_forward(eff[i:i + cap])[1] for i in range(0, F, cap)])
+
+        def image_embs():
+            return torch.cat([self.engine.clip_image(clp[i:i + cap]) for i in range(0, F, cap)])
+        dsc = rerun_if(self.engine.effnet_overflow, deepfake_scores, lambda d: d.cpu().numpy())
+        iemb = rerun_if(self.engine.clip_stream_overflow, image_embs)
         clip_mean = 0.0
         temb_vault = None
         if text:
             ids, mask = self._clip_ids([text])  # analyze_consistency: no truncation (Q8)
             temb = self.engine.clip_text(ids, mask)
-            if self.engine.clip_stream_overflow(temb):
+            if self.engine.clip_stream_overflow(temb):  # (not rerun_if: the image tower runs again as well)
                 temb = self.engine.clip_text(ids, mask)
-                iemb = torch.cat([self.engine.clip_image(clp[i:i + cap]) for i in range(0, F, cap)])
+                iemb = image_embs()
             # per-frame fp32 cosines (the reference's .item()), mean over python floats
             clip_mean = float(np.mean([float(v) for v in (iemb * temb).sum(1).cpu().numpy()]))
             tids, tmask = self._clip_ids([text], truncation=True)  # search_vault's caption
@@ -727,13 +727,13 @@ class MisinfoForensics:
             rid, rm, cid, cm, rgb = staged
             self._fit_text(rid.shape[1])
             eff, clp = self._windows(*rgb)
-            out = self.batch_to_host(self.analyze_batch(rid, rm, cid, cm, eff, clp))
             # run-time precision traps on the results already read back (no device launch: analyze()
             # at B = 1 -0.2 ms): a non-finite text score / deepfake score / clip_similarity (the cosine
             # of the two CLIP embeddings; a zero vault row's NaN stays in top_sims) means an fp16
             # stream overflowed -- that tower switches precision and the batch runs again
-            if self.engine.scores_overflow(out["scores"]):
-                out = self.batch_to_host(self.analyze_batch(rid, rm, cid, cm, eff, clp))
+            out = rerun_if(self.engine.scores_overflow,
+                           lambda: self.batch_to_host(self.analyze_batch(rid, rm, cid, cm, eff, clp)),
+                           lambda o: o["scores"])
             res.extend(self.batch_to_dicts(out))
 
         self._run_chunks(chunks, host_stage, device_part)
@@ -818,11 +818,11 @@ class MisinfoForensics:
             if rid is not None:
                 self._fit_text(rid.shape[1])
             eff, clp = self._windows(*rgb) if rgb is not None else (None, None)
-            out = self.batch_to_host(self.analyze_mixed(m, rid, rm, cid, cm, eff, clp))
             # the run-time precision traps of analyze_pairs on the scores read back (an absent signal's
             # 0 is finite)
-            if self.engine.scores_overflow(out["scores"]):
-                out = self.batch_to_host(self.analyze_mixed(m, rid, rm, cid, cm, eff, clp))
+            out = rerun_if(self.engine.scores_overflow,
+                           lambda: self.batch_to_host(self.analyze_mixed(m, rid, rm, cid, cm, eff, clp)),
+                           lambda o: o["scores"])
             res.extend(self.batch_to_dicts(out, modality=m))
 
         self._run_chunks(chunks, host_stage, device_part)
@@ -962,11 +962,10 @@ class CLIPSimilarityEngine:
                 raise ValueError("Text input must be a non-empty string")
             seqs = io_utils.tokenize_clip(self.processor, [text])
             ids, mask = io_utils.pad_ids(seqs, self.model.eos_token_id)
-            t = self.model.clip_text(ids, mask)
-            i = self.model.clip_image(io_utils.clip_pixels(image)[None])
-            if self.model.clip_stream_overflow(t, i):  # fp16 stream overflow: re-run on fp32 streams
-                t = self.model.clip_text(ids, mask)
-                i = self.model.clip_image(io_utils.clip_pixels(image)[None])
+            px = io_utils.clip_pixels(image)[None]
+            # (an overflowed fp16 stream: both towers once more on fp32 streams)
+            t, i = rerun_if(lambda ti: self.model.clip_stream_overflow(*ti),
+                            lambda: (self.model.clip_text(ids, mask), self.model.clip_image(px)))
             similarity = float((i * t).sum().item())
             label = "Match" if similarity >= self.threshold else "Mismatch"
             return similarity, label

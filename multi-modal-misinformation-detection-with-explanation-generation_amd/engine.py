@@ -10,7 +10,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import hip, io_utils
+from . import hip, io_utils, precision
 from .hip import check, ptr, stream_ptr
 
 SCORE_KEYS = ("ai_score", "misinfo_score", "deepfake_score", "clip_similarity", "vault_discrepancy")
@@ -28,11 +28,8 @@ def _as_np(v) -> np.ndarray:
 class Engine:
     """MI355X replica of the MisinfoForensics models on one device."""
 
-    EFFNET_PRECISIONS = ("auto", "fp16", "fp32")
-    # RoBERTa stream / operand precision -> option text_hilo (csrc/text_host.cpp run_text / run_text_precise):
-    # "auto" = the LayerNorm-bound layout (-1: fp16 or split stream) unless the load-time calibration
-    # selects "precise"; the others pin the mode ("fp16" / "split" also skip packing the precise weights)
-    TEXT_PRECISIONS = {"auto": -1, "fp16": 0, "split": 1, "precise": 2}
+    EFFNET_PRECISIONS = precision.EffnetGuard.CHOICES
+    TEXT_PRECISIONS = precision.TextGuard.CHOICES
 
     def __init__(self, device: int = 0, detector_state=None, clip_state=None, eos_token_id: int = 49407,
                  max_batch: int = 256, max_text_len: int = 128, max_clip_len: int = 77,
@@ -48,23 +45,13 @@ class Engine:
         check(self.lib.mmf_create(device, ctypes.byref(h)), "mmf_create")
         self.h = h
         self.eos_token_id = eos_token_id
-        self.effnet_precision = effnet_precision
-        self.text_precision = text_precision
-        self.effnet_check = None
-        self.text_check = None
-        # an MMF_TEXT_HILO / MMF_EFFNET_FP32 environment value pins the tower under "auto"
-        # (no calibration overrides it); so does a set_option of text_hilo / effnet_fp32 made after
-        # the engine's own last write (_auto_set records those writes)
-        self._auto_set = {}
-        if text_precision == "auto" and os.environ.get("MMF_TEXT_HILO"):
-            self.text_precision = "pinned"
-        else:
-            self._auto_write("text_hilo", self.TEXT_PRECISIONS[text_precision])
-        if effnet_precision == "auto" and os.environ.get("MMF_EFFNET_FP32"):
-            self.effnet_precision = "pinned"
-        elif effnet_precision == "auto":
-            self._auto_set["effnet_fp32"] = self.get_option("effnet_fp32")
-        self.clip_stream_check = None
+        # the precision policy (precision.py): an explicit choice, an MMF_TEXT_HILO / MMF_EFFNET_FP32
+        # environment value under "auto", or a set_option of text_hilo / effnet_fp32 made after the engine's
+        # own last write (the ledger records those) pins the tower against calibration and trap alike
+        self.ledger = precision.OptionLedger(self)
+        self.text_guard = precision.TextGuard(self, self.ledger, text_precision)
+        self.effnet_guard = precision.EffnetGuard(self, self.ledger, effnet_precision)
+        self.clip_guard = precision.ClipStreamGuard(self)
         self.vault_n = 0
         self._workspaces = {}
         if detector_state is not None:
@@ -97,76 +84,16 @@ class Engine:
     def ready(self) -> int:
         return self.lib.mmf_ready(self.h)
 
-    # fp16 CLIP streams: largest tolerated change of an image-text cosine (the quantity clip_similarity
-    # and the vault scores are made of) between fp16 and fp32 residual streams -- half of the
-    # north-star 1e-3 (the ordinary synthetic draw measures 2.3e-4, an outlier-feature draw 1.3e-4)
-    CLIP_STREAM_TOL = 5e-4
-
-    def check_clip_streams(self, n: int = 8) -> dict:
-        """Load-time guard of the fp16 CLIP residual streams (option clip_res16).
-
-        The pre-LN stream is a running sum, so unlike RoBERTa's post-LN stream no LayerNorm
-        parameter bounds it: trained weights with outlier features can push it past fp16's range
-        (65504) or far enough up that its rounding matters.  A calibration forward measures it: both
-        CLIP towers on n seeded images / captions with fp16 streams and again with fp32 streams; if
-        an embedding is non-finite or any of the n x n image-text cosines moves by more than
-        CLIP_STREAM_TOL, the fp32 streams stay selected.  Returns (and keeps as `clip_stream_check`)
-        the measured change."""
-        from . import synthetic as syn
-        if self.get_option("clip_res16") != 1:
-            return self.clip_stream_check or {}
-        n = max(1, min(n, self.max_batch))
-        imgs = torch.from_numpy(syn.images(n, 4099)).to(self.device)
-        ids, mask = syn.clip_ids(n, min(77, self.max_clip_len), 4099)
-
-        def cosines():
-            e = self.clip_image(imgs).double()
-            t = self.clip_text(ids, mask).double()
-            return e, t, e @ t.T  # unit rows: cosines
-        e16, t16, c16 = cosines()
-        self.set_option("clip_res16", 0)
-        e32, t32, c32 = cosines()
-        finite = bool(torch.isfinite(e16).all() and torch.isfinite(t16).all())
-        dcos = float((c16 - c32).abs().max()) if finite else float("inf")
-        demb = float(max((e16 - e32).abs().max(), (t16 - t32).abs().max())) if finite else float("inf")
-        ok = finite and dcos <= self.CLIP_STREAM_TOL
-        if ok:
-            self.set_option("clip_res16", 1)
-        self.clip_stream_check = {"max_dcos": dcos, "max_demb": demb, "fp16_streams": ok, "rows": n}
-        return self.clip_stream_check
-
-    def clip_stream_overflow(self, *outputs) -> bool:
-        """Run-time overflow trap of the fp16 CLIP streams: the load-time calibration
-        measures 8 seeded inputs, so it bounds nothing for later ones.  An input that drives a
-        stream past fp16's range turns the embedding non-finite, and clip_similarity / the vault
-        scores with it.  The synchronous API paths (which read their results back anyway) pass
-        their CLIP outputs here: if fp16 streams are selected and any value is non-finite, the
-        engine switches to fp32 streams for good and returns True, and the caller re-runs the
-        batch.  Drift short of overflow is what the calibration alone covers.  An output
-        may be a device tensor or a host array the caller already read back (checked on the host:
-        no device launch or extra synchronisation)."""
-        if self.get_option("clip_res16") != 1:
-            return False
-
-        def finite(v) -> bool:
-            return bool(np.isfinite(v).all()) if isinstance(v, np.ndarray) else bool(torch.isfinite(v).all())
-        if all(finite(v) for v in outputs if v is not None):
-            return False
-        self.set_option("clip_res16", 0)
-        self.clip_stream_check = dict(self.clip_stream_check or {}, fp16_streams=False, runtime_overflow=True)
-        return True
-
-    # fp16 EfficientNet tower: largest tolerated change of deepfake_score against the fp32 tower on
-    # the calibration images (half the north-star bar; the ordinary draw measures ~1e-4 over 256)
-    EFFNET_TOL = 5e-4
-
-    def _auto_write(self, name: str, value: int) -> None:
-        self.set_option(name, value)
-        self._auto_set[name] = int(value)
-
-    def _pinned(self, name: str) -> bool:
-        """True when the option was changed since the engine last wrote it (a user pin)."""
-        return name in self._auto_set and self.get_option(name) != self._auto_set[name]
+    # ------------------------------------------------------------------ precision guards
+    # (delegations: precision.py holds the calibrations, the traps and what counts as a user pin)
+    CLIP_STREAM_TOL = precision.ClipStreamGuard.TOL
+    EFFNET_TOL = precision.EffnetGuard.TOL
+    TEXT_TOL = precision.TextGuard.TOL
+    text_precision = property(lambda self: self.text_guard.choice)
+    effnet_precision = property(lambda self: self.effnet_guard.choice)
+    text_check = property(lambda self: self.text_guard.check)
+    effnet_check = property(lambda self: self.effnet_guard.check)
+    clip_stream_check = property(lambda self: self.clip_guard.check)
 
     def calibrate(self, components=("effnet",)) -> None:
         """Load-time precision selection for re-packed components (called at construction and by
@@ -177,164 +104,26 @@ class Engine:
         if "effnet" in components and self.ready & 2:
             self.check_effnet_precision()
 
-    # RoBERTa: largest tolerated change of ai_score / misinfo_score between the fast layout and the
-    # precise mode on the calibration texts (half the north-star bar)
-    TEXT_TOL = 5e-4
-
-    # precise-mode GEMM kinds (option text_prec_mask: bit k = kind k on hi / lo activations, bit k + 4 =
-    # also on W_lo; kinds QKV, out-proj, FFN-1, FFN-2) and their relative GEMM cost (the K loop is 1x /
-    # 2x / 3x): the calibration keeps the cheapest mask within TEXT_TOL of the full mode (255)
-    PREC_KIND_COST = (3, 1, 4, 4)
-    PREC_FULL = 255
-
-    @classmethod
-    def _mask_cost(cls, m: int) -> int:
-        return sum(c * (1 + (m >> k & 1) + (m >> k & 1) * (m >> (k + 4) & 1)) for k, c in enumerate(cls.PREC_KIND_COST))
-
-    @classmethod
-    def _prec_masks(cls):
-        """Every operand mask below the full mode, cheapest first (3 levels per kind)."""
-        import itertools
-        ms = [sum((lv >= 1) << k | (lv == 2) << (k + 4) for k, lv in enumerate(lvls))
-              for lvls in itertools.product((0, 1, 2), repeat=4)]
-        return sorted((m for m in ms if m != cls.PREC_FULL), key=lambda m: (cls._mask_cost(m), m))
+    def check_clip_streams(self, n: int = 8) -> dict:
+        return self.clip_guard.calibrate(n)
 
     def check_text_precision(self, n: int = 64) -> dict:
-        """Load-time selection of the RoBERTa text mode.  The
-        fp16-operand design holds 1e-3 only while the LayerNorms do not amplify operand rounding: a
-        checkpoint with one channel dominating every LayerNorm (gamma ~7: DESIGN.md §4) moves the
-        scores by 1.6e-3 even on the split stream.  With text_precision "auto", on n seeded texts of
-        128 tokens:
-          1. the fast layout (fp16 or split stream, from the LayerNorm bound) against the full
-             precise mode (fp32 stream / LayerNorm / attention, every GEMM on ~22-bit hi / lo
-             operands); within TEXT_TOL on every score -> the fast layout, and the precise weights
-             are released (the run-time trap falls back to the precise mode on fp16 operands,
-             which needs none of them);
-          2. otherwise every cheaper operand mask (option text_prec_mask: which GEMM kinds read hi / lo
-             operands, the rest fp16) against the full mode; the cheapest within TEXT_TOL is
-             selected and only its kinds' weights stay packed.
-        A user pin (text_precision other than "auto", MMF_TEXT_HILO, or a set_option of text_hilo
-        after the engine's last write) is left alone."""
-        from . import synthetic as syn
-        if self.text_precision != "auto" or self._pinned("text_hilo"):
-            self.text_check = {"mode": self.text_precision if self.text_precision != "auto" else "pinned",
-                               "calibrated": False}
-            return self.text_check
-        self._auto_write("text_hilo", -1)
-        n = max(1, n)
-        L = min(128, self.max_text_len)
-        ids, mask = syn.roberta_ids(n, L, 6007, [L, L // 2, 17, 5])
-
-        def scores():
-            return torch.cat([self.text_forward(ids[i:i + self.max_batch], mask[i:i + self.max_batch])[2].double()
-                              for i in range(0, n, self.max_batch)])
-
-        def dist(a, b):
-            return float((a - b).abs().max()) if bool(torch.isfinite(a).all()) else float("inf")
-        names = {0: "fp16", 1: "split", 2: "precise"}
-        fast = scores()
-        fast_mode = self.get_option("text_hilo_effective")
-        packed = self.get_option("text_precise_packed")
-        if packed != 15:  # (weights packed under a pinned layout: nothing to compare against)
-            self.text_check = {"mode": names[fast_mode], "calibrated": False, "precise_packed": packed}
-            return self.text_check
-        self.set_option("text_prec_mask", self.PREC_FULL)
-        self._auto_write("text_hilo", 2)
-        full = scores()
-        d = dist(fast, full)
-        self.text_check = {"max_dscore": d, "fast_layout": names[fast_mode], "texts": n, "calibrated": True}
-        if d <= self.TEXT_TOL:
-            self._auto_write("text_hilo", -1)
-            self.set_option("text_precise_packed", 0)  # ADVICE r5: the +510 MB go when the mode is not used
-            self.text_check["mode"] = names[fast_mode]
-            return self.text_check
-        tried = {}
-        best = self.PREC_FULL
-        for m in self._prec_masks():
-            self.set_option("text_prec_mask", m)
-            tried[m] = dist(scores(), full)
-            if tried[m] <= self.TEXT_TOL:
-                best = m
-                break
-        self.set_option("text_prec_mask", best)
-        self.set_option("text_precise_packed", best & 15)
-        self.text_check.update(mode="precise", prec_mask=best, mask_dscore=tried,
-                               cost_vs_full=self._mask_cost(best) / self._mask_cost(self.PREC_FULL))
-        return self.text_check
-
-    def text_overflow(self, scores) -> bool:
-        """Run-time overflow trap of the fast RoBERTa layouts (the counterpart of
-        clip_stream_overflow).  The load-time calibration bounds the drift on its seeded texts; an
-        input whose branch output passes fp16's range (a token driving an FFN-2 row past 65504) turns
-        that text's scores non-finite.  Given text scores the caller already read back: if a fast
-        layout is selected and any is non-finite, the engine switches to the precise mode for good
-        (fp32 stream and branch outputs; hi / lo operands for the kinds still packed, fp16 for the
-        rest) and returns True, and the caller re-runs the batch.  A pinned layout is left alone."""
-        if self.get_option("text_hilo_effective") >= 2 or self._pinned("text_hilo"):
-            return False
-        if bool(np.isfinite(np.asarray(scores)).all()):
-            return False
-        packed = self.get_option("text_precise_packed")
-        self.set_option("text_prec_mask", packed | packed << 4)
-        self._auto_write("text_hilo", 2)
-        self.text_check = dict(self.text_check or {}, mode="precise", runtime_overflow=True,
-                               prec_mask=self.get_option("text_prec_mask"))
-        return True
-
-    def effnet_overflow(self, scores) -> bool:
-        """Run-time overflow trap of the fp16 EfficientNet tower: given
-        deepfake scores the caller already read back, a non-finite one under the fp16 tower switches
-        the engine to the fp32 tower for good and returns True (the caller re-runs the batch).  An
-        image whose activation passes fp16's range (a saturated colour on a high-gain stem channel)
-        is what the load-time calibration on seeded images cannot see.  A pinned tower is left
-        alone."""
-        if self.get_option("effnet_fp32") != 0 or self.effnet_precision != "auto" or self._pinned("effnet_fp32"):
-            return False
-        if bool(np.isfinite(np.asarray(scores)).all()):
-            return False
-        self._auto_write("effnet_fp32", 1)
-        self.effnet_check = dict(self.effnet_check or {}, tower="fp32", runtime_overflow=True)
-        return True
-
-    def scores_overflow(self, scores5) -> bool:
-        """All three run-time traps on an analyze_batch result read back to the host ([B, 5]: ai,
-        misinfo, deepfake, clip_similarity, vault): True when any tower switched precision (the
-        caller re-runs the batch once)."""
-        s = np.asarray(scores5)
-        hit = self.text_overflow(s[:, :2])
-        hit = self.effnet_overflow(s[:, 2]) or hit
-        return self.clip_stream_overflow(s[:, 3]) or hit
+        return self.text_guard.calibrate(n)
 
     def check_effnet_precision(self, n: int = 64) -> dict:
-        """Load-time guard of the fp16 EfficientNet tower (the counterpart of
-        check_clip_streams).  A BN-conditioned tower is insensitive to fp16 activation storage; a
-        chaotic one (logits of O(100): He-gain draws) amplifies it to O(0.1).  With
-        effnet_precision "auto" both towers run on n seeded calibration images; if any deepfake_score
-        is non-finite or moves by more than EFFNET_TOL, the fp32 tower stays selected.  "fp16" /
-        "fp32" pin the tower without measuring.  Returns (and keeps as `effnet_check`) the result."""
-        from . import synthetic as syn
-        if self.effnet_precision != "auto" or self._pinned("effnet_fp32"):
-            if self.effnet_precision in ("fp16", "fp32"):
-                self.set_option("effnet_fp32", int(self.effnet_precision == "fp32"))
-            self.effnet_check = {"tower": self.effnet_precision if self.effnet_precision != "auto" else "pinned",
-                                 "calibrated": False}
-            return self.effnet_check
-        n = max(1, n)
-        imgs = torch.from_numpy(syn.images(n, 5003)).to(self.device)
+        return self.effnet_guard.calibrate(n)
 
-        def scores(fp32: int):
-            self._auto_write("effnet_fp32", fp32)
-            out = []
-            for i in range(0, n, self.max_batch):
-                out.append(self.effnet_forward(imgs[i:i + self.max_batch])[1].double())
-            return torch.cat(out)
-        s16, s32 = scores(0), scores(1)
-        finite = bool(torch.isfinite(s16).all())
-        d = float((s16 - s32).abs().max()) if finite else float("inf")
-        ok = finite and d <= self.EFFNET_TOL
-        self._auto_write("effnet_fp32", 0 if ok else 1)
-        self.effnet_check = {"max_ddeepfake": d, "tower": "fp16" if ok else "fp32", "images": n, "calibrated": True}
-        return self.effnet_check
+    def clip_stream_overflow(self, *outputs) -> bool:
+        return self.clip_guard.overflow(*outputs)
+
+    def text_overflow(self, scores) -> bool:
+        return self.text_guard.overflow(scores)
+
+    def effnet_overflow(self, scores) -> bool:
+        return self.effnet_guard.overflow(scores)
+
+    def scores_overflow(self, scores5) -> bool:
+        return precision.scores_overflow(self.text_guard, self.effnet_guard, self.clip_guard, scores5)
 
     # ------------------------------------------------------------------ options / accounting
     def set_option(self, name: str, value: int) -> None:
@@ -445,8 +234,8 @@ class Engine:
     def text_pooled(self, ids, mask):
         """The rows the ai / misinfo heads read (mmf_text_pooled): last_hidden_state[:, 0, :] float32 [B, 768]
         on the device, by text_forward's launch sequence without the heads.  The run-time trap of the
-        synchronous API paths (text_overflow): a non-finite row switches the tower to the precise mode and the
-        batch runs again."""
+        synchronous API paths (text_overflow): a non-finite row switches the tower, unless pinned, to the precise
+        mode and the batch runs again."""
         ids, mask = self._i32(ids), self._i32(mask)
         B, L = ids.shape
         cls = self._f32(B, 768)
@@ -454,10 +243,8 @@ class Engine:
         def run():
             check(self.lib.mmf_text_pooled(self.h, ptr(ids), ptr(mask), B, L, ptr(cls), stream_ptr()),
                   "mmf_text_pooled")
-        run()
-        if self.text_overflow((cls * 0).sum(1).cpu().numpy()):  # 0 or NaN per row
-            run()
-        return cls
+            return cls
+        return precision.rerun_if(self.text_overflow, run, lambda c: (c * 0).sum(1).cpu().numpy())  # 0 or NaN per row
 
     def effnet_forward(self, img):
         img = self._u8(img)
@@ -481,17 +268,15 @@ class Engine:
         """The row the deepfake classifier reads (mmf_effnet_pooled): the global average of the 7x7 head output,
         float32 [B, 1280] on the device, by effnet_forward's launch sequence for the tower in use without the
         classifier.  The run-time trap of the synchronous API paths (effnet_overflow): a non-finite row switches
-        the engine to the fp32 tower and the batch runs again."""
+        the engine, unless pinned, to the fp32 tower and the batch runs again."""
         img = self._u8(img)
         B = img.shape[0]
         pooled = self._f32(B, 1280)
 
         def run():
             check(self.lib.mmf_effnet_pooled(self.h, ptr(img), B, ptr(pooled), stream_ptr()), "mmf_effnet_pooled")
-        run()
-        if self.effnet_overflow((pooled * 0).sum(1).cpu().numpy()):  # 0 or NaN per row
-            run()
-        return pooled
+            return pooled
+        return precision.rerun_if(self.effnet_overflow, run, lambda p: (p * 0).sum(1).cpu().numpy())  # 0 or NaN per row
 
     def hflip(self, img):
         """A staged uint8 [B, H, W, C] window mirrored left-right (mmf_hflip_u8) into a new device tensor."""
@@ -546,10 +331,8 @@ class Engine:
         def run():
             check(self.lib.mmf_clip_pooled(self.h, ptr(img), ptr(ids), ptr(mask), B, ids.shape[1] if ids is not None
                                            else 1, ptr(ip), ptr(tp), stream_ptr()), "mmf_clip_pooled")
-        run()
-        if self.clip_stream_overflow(ip, tp):
-            run()
-        return ip, tp
+            return ip, tp
+        return precision.rerun_if(lambda rows: self.clip_stream_overflow(*rows), run)
 
     def set_clip_projections(self, visual=None, text=None) -> None:
         """Trained projection heads into the towers (mmf_set_clip_projections): float32 [512, 768] /

@@ -23,6 +23,7 @@ import torch
 from . import io_utils
 from . import training_common as TC
 from . import weights as W
+from .precision import rerun_if
 from .training_common import pack_keep, split_like as _split  # pack_keep here: bool [N, 64] -> uint64 [N]
 
 P_DROP = 0.2  # fusion_layer's Dropout (misinfo_forensics.py:86)
@@ -96,10 +97,9 @@ def extract_scores(forensics, texts: Sequence[str], image_paths: Sequence[str]) 
             rid, rm, cid, cm, rgb = st
             forensics._fit_text(rid.shape[1])
             eff, clp = forensics._windows(*rgb)
-            s = forensics.analyze_batch(rid, rm, cid, cm, eff, clp)["scores"].cpu().numpy()
-            if forensics.engine.scores_overflow(s):  # a tower switched precision: the batch runs again
-                s = forensics.analyze_batch(rid, rm, cid, cm, eff, clp)["scores"].cpu().numpy()
-            scores[rows] = s
+            # (a tower that switches precision on these scores: the batch runs again)
+            scores[rows] = rerun_if(forensics.engine.scores_overflow,
+                                    lambda: forensics.analyze_batch(rid, rm, cid, cm, eff, clp)["scores"].cpu().numpy())
             ok[rows] = True
         except Exception:  # noqa: BLE001
             for i in rows:

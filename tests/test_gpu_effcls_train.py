@@ -371,7 +371,7 @@ def test_effnet_pooled_on_the_golden_images(engine, det_sd, golden_inputs, oracl
             assert torch.equal(a, b)
         assert engine.get_option("effnet_fp32") == fp32
     finally:
-        engine.set_option("effnet_fp32", engine._auto_set.get("effnet_fp32", 0))
+        engine.set_option("effnet_fp32", engine.ledger.last("effnet_fp32", 0))
     pooled = pooled.cpu().numpy()
     assert pooled.shape == (B, 1280) and pooled.dtype == np.float32 and np.isfinite(pooled).all()
     # the classifier in float64 on the pooled rows against the tower's own logits: the fp32 bound of its sum

@@ -101,12 +101,12 @@ def test_effnet_runtime_overflow_trap(det_sd, clip_sd):
     want = mf.engine.effnet_forward(arrs)[1].cpu().numpy()
     want_pairs = [d["scores"] for d in mf.analyze_pairs(texts, imgs)]
     mf.engine.set_option("effnet_fp32", 0)
-    mf.engine._auto_set["effnet_fp32"] = 0  # (back to the calibrated state: not a user pin)
+    mf.engine.ledger.record("effnet_fp32")  # (back to the calibrated state: not a user pin)
     got = mf.analyze_image(imgs[1])["deepfake_score"]
     assert mf.engine.get_option("effnet_fp32") == 1 and mf.engine.effnet_check["runtime_overflow"]
     assert np.isfinite(got) and abs(got - want[1]) < 1e-6
     mf.engine.set_option("effnet_fp32", 0)
-    mf.engine._auto_set["effnet_fp32"] = 0
+    mf.engine.ledger.record("effnet_fp32")
     got_pairs = [d["scores"] for d in mf.analyze_pairs(texts, imgs)]
     assert mf.engine.get_option("effnet_fp32") == 1
     for g, w in zip(got_pairs, want_pairs):
@@ -147,11 +147,11 @@ def test_text_runtime_overflow_trap(det_sd, clip_sd):
     mf.engine.set_option("text_hilo", 2)
     want = mf.engine.text_forward(ids, np.ones_like(ids))[2].cpu().numpy()
     want_pairs = [d["scores"] for d in mf.analyze_pairs(texts, imgs)]
-    mf.engine._auto_write("text_hilo", -1)
+    mf.engine.ledger.write("text_hilo", -1)
     got = mf.analyze_text(texts[2])
     assert mf.engine.get_option("text_hilo_effective") == 2 and mf.engine.text_check["runtime_overflow"]
     assert abs(got["ai_score"] - want[2, 0]) < 1e-6 and abs(got["misinfo_score"] - want[2, 1]) < 1e-6
-    mf.engine._auto_write("text_hilo", -1)
+    mf.engine.ledger.write("text_hilo", -1)
     got_pairs = [d["scores"] for d in mf.analyze_pairs(texts, imgs)]
     assert mf.engine.get_option("text_hilo_effective") == 2
     for g, w in zip(got_pairs, want_pairs):
