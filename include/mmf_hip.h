@@ -149,6 +149,29 @@ int mmf_effnet_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, v
  * nothing launched: a NULL pointer, a non-positive dimension, dst == src. */
 int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, void* stream);
 
+/* ColorJitter on staged uint8 windows (train_cifake_forensics.py:39-45: Resize, the flip, then
+ * ColorJitter(0.2, 0.2, 0.2, 0.1), all before ToTensor), byte-exact with what torchvision's PIL backend computes
+ * with Pillow: ImageEnhance.Brightness / Contrast / Color (Image.blend against black / the rounded mean of L / L)
+ * and, for the hue, convert("HSV"), a uint8 wrap-around add on H and convert("RGB").  src, dst uint8 [B][H][W][3],
+ * any H, W >= 1; dst and src must not overlap.  No handle; two ordinary launches on `stream`, no atomics: the
+ * first forms, for images whose chain holds a contrast, the sum of L of the image as it stands at that point of
+ * the chain (integer partial sums per chunk of pixels in ws, so the result does not depend on any order), the
+ * second applies the chain.
+ *   ops int32 [B][4]: the k-th operation applied to image b: 0 brightness, 1 contrast, 2 saturation, 3 hue,
+ *     -1 skip.  The result of every operation is rounded to uint8 before the next, as in the PIL chain.  A chain
+ *     holds at most one contrast: a second one is skipped, as is any code outside -1..3.
+ *   factors fp32 [B][3]: brightness, contrast, saturation (the blend factor: 1 keeps the image; 0 <= f <= 1
+ *     truncates, any other factor clips, as Image.blend does).
+ *   hue_shift int32 [B]: what is added to H, taken & 255 (torchvision: uint8(hue_factor * 255)).  A hue operation
+ *     with shift 0 still makes the HSV round trip, which is not the identity.
+ *   ws uint64 [B][MMF_JITTER_CHUNKS], 8-byte aligned; contents on entry do not matter.
+ * No value in the device arrays can make a kernel read or write out of bounds.  MMF_EINVAL with nothing launched
+ * and dst untouched: a NULL pointer, a non-positive dimension, B > 65535 (the grid), H * W > 2^40 (the sum of L
+ * must stay exact in a double), dst == src, ops / factors / hue_shift not 4-byte aligned, ws not 8-byte. */
+#define MMF_JITTER_CHUNKS 256
+int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops, const float* factors,
+                        const int32_t* hue_shift, uint64_t* ws, void* stream);
+
 /* Training of the deployed deepfake classifier -- Dropout(0.2) then Linear(1280, 2) on the pooled row
  * (misinfo_forensics.py:72-76) -- on cached pooled rows (train_cifake_forensics.py:187-216 the loop body, stated
  * for a frozen backbone): ONE epoch in ONE launch by one workgroup.  For each of the ceil(N / batch)

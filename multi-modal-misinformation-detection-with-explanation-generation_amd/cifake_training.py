@@ -9,7 +9,11 @@ and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads
 * ``extract_image_features``: the pooled 1280-wide row of every image, once, through the HIP tower
   (``Engine.effnet_pooled``) -- and, for the training transform's RandomHorizontalFlip, the row of the mirrored
   window (``mmf_hflip_u8`` on the staged window, after the Pillow-exact resize: Resize, then the flip, :39-45).
-* ``plan``: per epoch the permutation, the flip draws and the dropout masks.
+  With ``jitter`` the rows of K colour-jittered views of every image: the script's ColorJitter(0.2, 0.2, 0.2, 0.1)
+  on the staged window, byte-exact with torchvision's PIL backend (``mmf_color_jitter_u8``), no window leaving the
+  device.
+* ``jitter_params``: per view and image the order of the four operations, the three factors and the hue shift.
+* ``plan``: per epoch the permutation, the flip draws and the dropout masks; with views, epoch e trains on view e % K.
 * ``ClassifierTrainer``: one ``mmf_effcls_train_epoch`` and one ``mmf_effcls_eval`` call per epoch on the cached
   rows, a raw state dict on a strictly higher validation accuracy (:372-374), the best classifier put back into
   the detector.
@@ -17,10 +21,11 @@ and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads
 
 Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a frozen backbone, where the script
 fine-tunes the whole backbone together with a 1538-d fusion head of another model class.  Further: the deployed
-ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; no ColorJitter, and the flip
-comes from two cached views; fp32, no autocast / GradScaler; a seeded generator instead of the global RNG; file names
-sorted before the seeded shuffle (os.listdir order is arbitrary); unreadable images dropped instead of fed as a blank
-tensor.
+ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; the flip comes from two
+cached views, and ColorJitter from ``jitter_views`` cached views (0 by default: none; K = epochs gives every image a
+fresh draw in every epoch, as the script's DataLoader does); fp32, no autocast / GradScaler; a seeded generator
+instead of the global RNG; file names sorted before the seeded shuffle (os.listdir order is arbitrary); unreadable
+images dropped instead of fed as a blank tensor.
 """
 from __future__ import annotations
 
@@ -85,16 +90,58 @@ def load_cifake_data(cifake_root: str, sample_per_label: int = 2500, seed: int =
 # ---------------------------------------------------------------------------------------------
 # cached features
 # ---------------------------------------------------------------------------------------------
-def extract_image_features(forensics, image_paths: Sequence, flip: bool = False):
+def jitter_params(N: int, views: int, seed: int, brightness: float = 0.2, contrast: float = 0.2,
+                  saturation: float = 0.2, hue: float = 0.1):
+    """ColorJitter.get_params for ``views`` views of N images -> (ops int32 [views, N, 4], factors float32
+    [views, N, 3], hue_shift int32 [views, N]), the arguments of ``Engine.color_jitter`` per view.  From one
+    ``torch.Generator().manual_seed(seed)``, in this order: the order of the four operations as the argsort of
+    ``torch.rand(views, N, 4)`` (a uniform random permutation, as get_params' ``torch.randperm(4)``); the
+    brightness, contrast and saturation factors uniform in [max(0, 1 - x), 1 + x] in float32; the hue factor
+    uniform in [-hue, hue] in float64, turned into the H shift as adjust_hue does, ``uint8(hue_factor * 255)``:
+    truncated toward zero, then mod 256.  A zero range leaves its operation out of the chain (-1), as
+    torchvision's None does; its draw is still taken, so the other draws do not depend on it."""
+    g = torch.Generator().manual_seed(int(seed))
+    ops = torch.argsort(torch.rand(views, N, 4, generator=g), dim=-1).numpy().astype(np.int32)
+    ranges = (float(brightness), float(contrast), float(saturation))
+    factors = np.ones((views, N, 3), np.float32)
+    for k, x in enumerate(ranges):
+        if x < 0:
+            raise ValueError(f"jitter_params: a negative range {x}")
+        draw = torch.empty(views, N, dtype=torch.float32).uniform_(max(0.0, 1.0 - x), 1.0 + x, generator=g).numpy()
+        if x > 0:
+            factors[..., k] = draw
+    if not 0 <= float(hue) <= 0.5:
+        raise ValueError(f"jitter_params: hue must be in [0, 0.5], got {hue}")
+    h = torch.empty(views, N, dtype=torch.float64).uniform_(-float(hue), float(hue), generator=g).numpy()
+    hue_shift = (np.trunc(h * 255).astype(np.int64) % 256).astype(np.int32)
+    for k, x in enumerate(ranges + (float(hue),)):
+        if x == 0:
+            ops[ops == k] = -1
+    return ops, factors, hue_shift
+
+
+def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None):
     """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
     the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
     staged as analyze_pairs stages them (device JPEG decode where it applies, Pillow otherwise, the Pillow-exact
     squash to 224 x 224 on the device), the window mirrored on the device, both through ``Engine.effnet_pooled``.
-    An image that cannot be read gives ok False and zero rows."""
+    An image that cannot be read gives ok False and zero rows.
+
+    ``jitter`` = (ops, factors, hue_shift) of ``jitter_params(N, views, ...)``: the rows become float32
+    [views, N, 1280] (both of them with ``flip``), view v being the staged window after ``Engine.color_jitter``
+    with draw v.  Every operation is per pixel or a whole-image mean, so jitter and flip commute exactly: the
+    mirrored view is the mirror of the jittered window."""
     paths = list(image_paths)
     N = len(paths)
-    feats = np.zeros((N, WIDTH), np.float32)
-    flipped = np.zeros((N, WIDTH), np.float32) if flip else None
+    if jitter is not None:
+        j_ops, j_fac, j_hue = (np.asarray(a) for a in jitter)
+        views = j_ops.shape[0]
+        if j_ops.shape != (views, N, 4) or j_fac.shape != (views, N, 3) or j_hue.shape != (views, N) or views < 1:
+            raise ValueError(f"jitter: expected ops [K, {N}, 4], factors [K, {N}, 3], hue_shift [K, {N}], K >= 1, got "
+                             f"{j_ops.shape}, {j_fac.shape}, {j_hue.shape}")
+    shape = (N, WIDTH) if jitter is None else (views, N, WIDTH)
+    feats = np.zeros(shape, np.float32)
+    flipped = np.zeros(shape, np.float32) if flip else None
     ok = np.ones(N, bool)
     cap = forensics.engine.max_batch
     chunks = [(a, min(a + cap, N)) for a in range(0, N, cap)]
@@ -118,15 +165,23 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False)
     def device_part(staged):
         a, b, rgb = staged
         eff, _ = forensics._windows(*rgb)
-        feats[a:b] = forensics.engine.effnet_pooled(eff).cpu().numpy()
-        if flip:
-            flipped[a:b] = forensics.engine.effnet_pooled(forensics.engine.hflip(eff)).cpu().numpy()
+        eng = forensics.engine
+        if jitter is None:
+            feats[a:b] = eng.effnet_pooled(eff).cpu().numpy()
+            if flip:
+                flipped[a:b] = eng.effnet_pooled(eng.hflip(eff)).cpu().numpy()
+            return
+        for v in range(views):
+            win = eng.color_jitter(eff, j_ops[v, a:b], j_fac[v, a:b], j_hue[v, a:b])
+            feats[v, a:b] = eng.effnet_pooled(win).cpu().numpy()
+            if flip:
+                flipped[v, a:b] = eng.effnet_pooled(eng.hflip(win)).cpu().numpy()
 
     if chunks:
         forensics._run_chunks(chunks, host_stage, device_part)
-    feats[~ok] = 0
+    feats[..., ~ok, :] = 0
     if flip:
-        flipped[~ok] = 0
+        flipped[..., ~ok, :] = 0
         return feats, flipped, ok
     return feats, ok
 
@@ -137,19 +192,26 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False)
 unpack_keep = functools.partial(TC.unpack_keep, width=WIDTH)  # uint64 [N, 20] -> bool [N, 1280]
 
 
-def plan(N: int, batch_size: int, epochs: int, seed: int, flip: bool = True):
+def plan(N: int, batch_size: int, epochs: int, seed: int, flip: bool = True, views: int = 0):
     """Per epoch (perm int32 [N], keep uint64 [N, 20], flipped bool [N]) from one
     ``torch.Generator().manual_seed(seed)``: the DataLoader's shuffle as ``torch.randperm(N)``; with ``flip`` the
     RandomHorizontalFlip draws ``torch.rand(N) < 0.5`` indexed by data-set row (all False without); the dropout
     masks ``torch.rand(N, 1280) >= 0.2`` (row i = the row at position i of the epoch order).  ``perm`` holds the
-    KERNEL's entries: row + N where the row is flipped, the mirrored view being rows N .. 2N - 1 of the bank."""
+    KERNEL's entries: row + N where the row is flipped, the mirrored view being rows N .. 2N - 1 of the bank.
+
+    ``views`` = K > 0 colour-jittered views take no further draw: epoch e (from 0) trains on view e % K, and the
+    bank is K blocks in view order -- with ``flip`` each block the view's rows, then its mirrored rows, the entry
+    row + N (2 view + flipped); without, the entry row + N view."""
     g = torch.Generator().manual_seed(int(seed))
     out = []
-    for _ in range(int(epochs)):
+    for e in range(int(epochs)):
         order = torch.randperm(N, generator=g).numpy().astype(np.int64)
         flipped = (torch.rand(N, generator=g) < 0.5).numpy() if flip else np.zeros(N, bool)
         keep = pack_keep((torch.rand(N, WIDTH, generator=g) >= P_DROP).numpy())
-        out.append(((order + N * flipped[order]).astype(np.int32), keep, flipped))
+        block = flipped[order].astype(np.int64)
+        if views > 0:
+            block = (2 * (e % views) + block) if flip else np.full(N, e % views, np.int64)
+        out.append(((order + N * block).astype(np.int32), keep, flipped))
     return out
 
 
@@ -175,9 +237,12 @@ class ClassifierTrainer:
     (``detector.sync``), which also re-runs the load-time precision calibration on the new classifier."""
 
     def __init__(self, forensics, batch_size: int = 16, epochs: int = 10, lr: float = 1e-4, seed: int = 0,
-                 flip: bool = True, weight_decay: float = WEIGHT_DECAY):
+                 flip: bool = True, weight_decay: float = WEIGHT_DECAY, jitter_views: int = 0):
         if not 1 <= int(batch_size) <= 64:
             raise ValueError(f"batch_size must be in 1..64, got {batch_size}")
+        if int(jitter_views) < 0:
+            raise ValueError(f"jitter_views must be >= 0, got {jitter_views}")
+        self.jitter_views = int(jitter_views)
         self.forensics, self.batch_size, self.epochs = forensics, int(batch_size), int(epochs)
         self.lr, self.seed, self.flip, self.weight_decay = float(lr), int(seed), bool(flip), float(weight_decay)
 
@@ -187,19 +252,29 @@ class ClassifierTrainer:
 
     def fit(self, train, train_labels, val, val_labels, checkpoint_path: Optional[str] = None,
             save_full_model: bool = False) -> List[dict]:
-        """``train``: float32 [N, 1280], or with ``flip`` the pair (rows, rows of the mirrored windows)."""
+        """``train``: float32 [N, 1280], or with ``flip`` the pair (rows, rows of the mirrored windows); with
+        ``jitter_views`` = K each of them float32 [K, N, 1280], as ``extract_image_features(jitter=...)`` returns."""
         f = self.forensics
         eng, det = f.engine, f.detector
         dev = eng.device
-        if self.flip:
-            if not (isinstance(train, (tuple, list)) and len(train) == 2):
-                raise ValueError("flip=True needs train = (features, features of the mirrored windows)")
-            xt, yt = self._data(train[0], train_labels, "training")
-            xf, _ = self._data(train[1], train_labels, "mirrored training")
-            bank, bank_labels = np.concatenate([xt, xf]), np.concatenate([yt, yt])
+        K = self.jitter_views
+        if self.flip and not (isinstance(train, (tuple, list)) and len(train) == 2):
+            raise ValueError("flip=True needs train = (features, features of the mirrored windows)")
+        parts = tuple(train) if self.flip else (train,)
+        if K:
+            parts = tuple(np.asarray(p) for p in parts)
+            if any(p.ndim != 3 or p.shape[0] != K for p in parts):
+                raise ValueError(f"jitter_views={K} needs training features [{K}, N, {WIDTH}], got "
+                                 f"{[p.shape for p in parts]}")
+        # the bank's blocks in plan()'s order: per view its rows, then (flip) its mirrored rows
+        blocks = [p[v] if K else p for v in range(max(K, 1)) for p in parts]
+        names = ("training", "mirrored training")
+        blocks = [self._data(x, train_labels, names[i % len(parts)]) for i, x in enumerate(blocks)]
+        yt = blocks[0][1]
+        if len(blocks) == 1:
+            bank, bank_labels = blocks[0]
         else:
-            bank, bank_labels = self._data(train, train_labels, "training")
-            yt = bank_labels
+            bank, bank_labels = np.concatenate([x for x, _ in blocks]), np.concatenate([yt] * len(blocks))
         xv, yv = self._data(val, val_labels, "validation")
         N, bs = len(yt), self.batch_size
         bank, bank_labels, xv, yv_d = (torch.from_numpy(a).to(dev) for a in (bank, bank_labels, xv, yv))
@@ -207,7 +282,7 @@ class ClassifierTrainer:
         m, v = torch.zeros_like(params), torch.zeros_like(params)
         spe = -(-N // bs)
         history, best_acc, best, step0 = [], 0.0, None, 0
-        for epoch, (perm, keep, _) in enumerate(plan(N, bs, self.epochs, self.seed, self.flip), 1):
+        for epoch, (perm, keep, _) in enumerate(plan(N, bs, self.epochs, self.seed, self.flip, K), 1):
             sl, sc = eng.effcls_train_epoch(bank, bank_labels, torch.from_numpy(perm).to(dev),
                                             torch.from_numpy(keep.view(np.int64)).to(dev), P_DROP, bs, self.lr, BETAS,
                                             EPS, self.weight_decay, step0, params, m, v)
@@ -255,25 +330,29 @@ class ClassifierTrainer:
 # ---------------------------------------------------------------------------------------------
 def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epochs: int = 10,
                  sample_per_label: int = 2500, forensics=None, checkpoint_path: Optional[str] = DEFAULT_FILE, *,
-                 device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False):
+                 device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False,
+                 jitter_views: int = 0):
     """train_cifake_forensics.py:276-379: the CIFAKE tree's balanced sample and split, one feature extraction per
-    split (two views of the training images with ``flip``), unreadable images dropped and counted, then the trainer.
-    Returns the history."""
+    split (two views of the training images with ``flip``; with ``jitter_views`` = K, K colour-jittered draws of
+    each, from ``jitter_params(N, K, seed)``), unreadable images dropped and counted, then the trainer.  Returns the
+    history."""
     tr_p, tr_y, va_p, va_y = load_cifake_data(cifake_root, sample_per_label)
     print(f"Loaded {len(tr_p)} training samples ({tr_y.count(0)} REAL, {tr_y.count(1)} FAKE)")
     print(f"Loaded {len(va_p)} validation samples ({va_y.count(0)} REAL, {va_y.count(1)} FAKE)")
     if forensics is None:
         from .api import MisinfoForensics
         forensics = MisinfoForensics(device=device)
-    out = extract_image_features(forensics, tr_p, flip=flip)
+    jitter = jitter_params(len(tr_p), jitter_views, seed) if jitter_views else None
+    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter)
     ok_t = out[-1]
     xv, ok_v = extract_image_features(forensics, va_p)
     dropped = int((~ok_t).sum() + (~ok_v).sum())
     if dropped:
         print(f"Dropped {dropped} unreadable images")
     tr_y, va_y = np.asarray(tr_y)[ok_t], np.asarray(va_y)[ok_v]
-    train = (out[0][ok_t], out[1][ok_t]) if flip else out[0][ok_t]
-    trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip)
+    train = (out[0][..., ok_t, :], out[1][..., ok_t, :]) if flip else out[0][..., ok_t, :]
+    trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip,
+                                jitter_views=jitter_views)
     history = trainer.fit(train, tr_y, xv[ok_v], va_y, checkpoint_path=checkpoint_path,
                           save_full_model=save_full_model)
     for h in history:
@@ -292,10 +371,13 @@ def main(argv=None) -> None:
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--samples-per-label", type=int, default=2500)
     ap.add_argument("--no-flip", action="store_true", help="train on the unmirrored view alone")
+    ap.add_argument("--jitter-views", type=int, default=0, metavar="K",
+                    help="ColorJitter(0.2, 0.2, 0.2, 0.1): K cached draws per image, epoch e trains on draw e %% K "
+                         "(0: none; the number of epochs: a fresh draw per image and epoch, as the script)")
     ap.add_argument("--checkpoint", default=DEFAULT_FILE)
     a = ap.parse_args(argv)
     train_cifake(a.root, batch_size=a.batch_size, lr=a.lr, epochs=a.epochs, sample_per_label=a.samples_per_label,
-                 checkpoint_path=a.checkpoint, flip=not a.no_flip)
+                 checkpoint_path=a.checkpoint, flip=not a.no_flip, jitter_views=a.jitter_views)
 
 
 if __name__ == "__main__":

@@ -829,6 +829,20 @@ int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, v
   return 0;
 }
 
+static_assert(kJitterChunks == MMF_JITTER_CHUNKS, "header and kernels");
+int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops, const float* factors,
+                        const int32_t* hue_shift, uint64_t* ws, void* stream) {
+  if (!src || !dst || !ops || !factors || !hue_shift || !ws) return fail(MMF_EINVAL, "null argument");
+  if (B < 1 || B > kJitterMaxBatch || H < 1 || W < 1 || (double)H * W > (double)kJitterMaxPixels)
+    return fail(MMF_EINVAL, "color_jitter_u8: bad shape (B=%d (1..%d) H=%d W=%d (H*W <= 2^40))", B, kJitterMaxBatch, H,
+                W);
+  if (dst == src) return fail(MMF_EINVAL, "color_jitter_u8: dst must not be src");
+  if ((((uintptr_t)ops | (uintptr_t)factors | (uintptr_t)hue_shift) & 3) || ((uintptr_t)ws & 7))
+    return fail(MMF_EINVAL, "color_jitter_u8: ops, factors and hue_shift must be 4-byte aligned, ws 8-byte");
+  HIPCHK(launch_color_jitter_u8(src, dst, B, H, W, ops, factors, hue_shift, ws, (hipStream_t)stream));
+  return 0;
+}
+
 int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, const int32_t* perm, int N,
                            const uint64_t* keep, float p_drop, int batch, double lr, double beta1, double beta2,
                            double eps, double weight_decay, int step0, float* params, float* exp_avg,

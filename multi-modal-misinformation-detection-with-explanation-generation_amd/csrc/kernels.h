@@ -220,6 +220,14 @@ hipError_t launch_effcls_eval(const float* feat, const int32_t* labels, int R, i
                               float* batch_loss, float* row_logits, hipStream_t s);
 // dst[b][y][x][c] = src[b][y][W - 1 - x][c] (uint8; mmf_hflip_u8)
 hipError_t launch_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, hipStream_t s);
+// ColorJitter on uint8 [B][H][W][3], byte-exact with torchvision's PIL backend (jitter.hip; include/mmf_hip.h
+// mmf_color_jitter_u8): two launches, grid (chunks <= kJitterChunks, B); ws uint64 [B][kJitterChunks] holds the
+// chunks' sums of L for the contrast mean; hipErrorInvalidValue on a bad shape with nothing launched
+constexpr int kJitterChunks = 256;                   // MMF_JITTER_CHUNKS
+constexpr int kJitterMaxBatch = 65535;               // the grid's y extent
+constexpr size_t kJitterMaxPixels = (size_t)1 << 40; // per image: 255 * pixels stays exact in a double (< 2^53)
+hipError_t launch_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops,
+                                  const float* factors, const int32_t* hue_shift, uint64_t* ws, hipStream_t s);
 // the CLS rows the text heads read: out fp32 [B][768] = x[b * row_stride ..]; a sequence with ovf[b] != 0 (nullable)
 // gets a NaN row, as launch_text_heads gives it NaN logits
 hipError_t launch_text_cls_rows(const float* x, int row_stride, const int* ovf, float* out, int B, hipStream_t s);

@@ -289,6 +289,29 @@ class Engine:
         check(self.lib.mmf_hflip_u8(ptr(t), ptr(out), B, H, Wd, C, stream_ptr()), "mmf_hflip_u8")
         return out
 
+    def color_jitter(self, img, ops, factors, hue_shift):
+        """torchvision's ColorJitter on staged uint8 [B, H, W, 3] windows (mmf_color_jitter_u8), byte-exact with its
+        PIL backend, into a new device tensor.  Per image: ``ops`` int32 [B, 4] the operations in the order applied
+        (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 skip), ``factors`` float32 [B, 3] (brightness, contrast,
+        saturation), ``hue_shift`` int32 [B] what is added to H (0..255)."""
+        t = self._tensor(img)
+        if not (t.dtype == torch.uint8 and t.dim() == 4 and t.numel() > 0 and t.shape[3] == 3):
+            raise ValueError(f"color_jitter: expected a non-empty uint8 [B, H, W, 3] tensor, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+        t = t.to(self.device).contiguous()
+        B, H, Wd, _ = t.shape
+        ops = torch.as_tensor(ops, dtype=torch.int32).to(self.device).contiguous()
+        factors = torch.as_tensor(factors, dtype=torch.float32).to(self.device).contiguous()
+        hue_shift = torch.as_tensor(hue_shift, dtype=torch.int32).to(self.device).contiguous()
+        if tuple(ops.shape) != (B, 4) or tuple(factors.shape) != (B, 3) or tuple(hue_shift.shape) != (B,):
+            raise ValueError(f"color_jitter: expected ops [{B}, 4], factors [{B}, 3], hue_shift [{B}], got "
+                             f"{tuple(ops.shape)}, {tuple(factors.shape)}, {tuple(hue_shift.shape)}")
+        out = torch.empty_like(t)
+        ws = torch.empty((B, hip.JITTER_CHUNKS), dtype=torch.int64, device=self.device)
+        check(self.lib.mmf_color_jitter_u8(ptr(t), ptr(out), B, H, Wd, ptr(ops), ptr(factors), ptr(hue_shift), ptr(ws),
+                                           stream_ptr()), "mmf_color_jitter_u8")
+        return out
+
     def clip_image(self, img):
         img = self._u8(img)
         e = self._f32(img.shape[0], 512)
