@@ -172,6 +172,29 @@ int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, v
 int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops, const float* factors,
                         const int32_t* hue_shift, uint64_t* ws, void* stream);
 
+/* RandomJPEGCompression on staged uint8 windows (misinformation_dataset.py:18-57: the image saved as a JPEG at a
+ * random quality and loaded back), byte-exact with Pillow's Image.save(format="JPEG", quality=q, optimize=False)
+ * followed by Image.open(...).convert("RGB").  Huffman coding is lossless, so no bit stream is formed: libjpeg's
+ * forward half (RGB -> YCbCr, 4:2:0 downsampling with the edges replicated, the islow forward DCT, quantisation by
+ * jpeg_set_quality's tables) runs straight into the inverse half of the device decoder below (dequantisation, the
+ * islow IDCT, fancy upsampling, YCbCr -> RGB).  src, dst uint8 [B][H][W][3], any H, W >= 1; dst and src must not
+ * overlap.  No handle, no atomics; on `stream`: flags cleared, then two ordinary launches (per 8x8 block of a
+ * component everything up to the range-limited samples, in registers, into ws; per pixel the upsampling and the
+ * colour conversion).
+ *   quality int32 [B]: 1..100, or 0: image b is copied unchanged.  Any other value is treated as 0.
+ *   ws: mmf_jpeg_roundtrip_ws_bytes(H, W) bytes per image (host-only; 0 for a shape the call rejects), 8-byte
+ *     aligned: the sample planes; contents on entry do not matter.
+ *   flags int32 [B], written by the call: 0, or 1 where a block of image b left the exact range of the decoder
+ *     (see "The exact range" below; the three conditions are evaluated on the block's own values).  dst[b] is then
+ *     not Pillow's bytes and the caller redoes that image on the host.  No block made from pixels has been seen to
+ *     leave the range.
+ * No value in the device arrays can make a kernel read or write out of bounds.  MMF_EINVAL with nothing launched
+ * and dst untouched: a NULL pointer, a non-positive dimension, B > 65535 (the grid), H * W > 2^30 (pixel indices
+ * are ints), dst == src, quality / flags not 4-byte aligned, ws not 8-byte. */
+int64_t mmf_jpeg_roundtrip_ws_bytes(int H, int W);
+int mmf_jpeg_roundtrip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* quality, uint8_t* ws,
+                          int32_t* flags, void* stream);
+
 /* Training of the deployed deepfake classifier -- Dropout(0.2) then Linear(1280, 2) on the pooled row
  * (misinfo_forensics.py:72-76) -- on cached pooled rows (train_cifake_forensics.py:187-216 the loop body, stated
  * for a frozen backbone): ONE epoch in ONE launch by one workgroup.  For each of the ceil(N / batch)
@@ -823,6 +846,17 @@ int mmf_vault_topk_f32(const float* S, int B, int N, int k, float thresh, float*
 int mmf_vault_sort_cand_f32(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
                             float thresh, float* sims, int32_t* idx, float* disc, int disc_stride, const float* temb,
                             const float* title, int D, float* tsim, void* stream);
+
+/* Test-only: the block arithmetic of mmf_jpeg_roundtrip_u8 on raw operands (csrc/test_host.cpp; device pointers).
+ * blocks int16 [n][64]: level-shifted samples (sample - 128), row-major 8x8; table uint8 [64]: a quantisation table
+ * in natural order.  Per block the forward DCT, quantisation, dequantisation and IDCT of the round trip: coefs
+ * int16 [n][64] the quantised coefficients (natural order), samples uint8 [n][64] the range-limited result,
+ * outside int32 [n] 1 where the block left the exact range (what sets flags there; samples mean nothing then),
+ * else 0.  Synchronous: the operands are read back and checked first.  MMF_EINVAL with nothing launched: a NULL
+ * pointer, n outside 1..2^20, a misaligned pointer, a sample outside +-1024 (up to there 32-bit arithmetic is
+ * exact; pixels give +-128), a zero table entry. */
+int mmf_jpeg_block_roundtrip_raw(const int16_t* blocks, const uint8_t* table, int n, int16_t* coefs, uint8_t* samples,
+                                 int32_t* outside, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,10 @@ and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads
   window (``mmf_hflip_u8`` on the staged window, after the Pillow-exact resize: Resize, then the flip, :39-45).
   With ``jitter`` the rows of K colour-jittered views of every image: the script's ColorJitter(0.2, 0.2, 0.2, 0.1)
   on the staged window, byte-exact with torchvision's PIL backend (``mmf_color_jitter_u8``), no window leaving the
-  device.
+  device.  With ``jpeg`` the rows of K views saved as JPEGs at given qualities and loaded back, the reference's
+  RandomJPEGCompression (misinformation_dataset.py:18-57), byte-exact with Pillow (``mmf_jpeg_roundtrip_u8``).
 * ``jitter_params``: per view and image the order of the four operations, the three factors and the hue shift.
+* ``jpeg_params``: per view and image the JPEG quality.
 * ``plan``: per epoch the permutation, the flip draws and the dropout masks; with views, epoch e trains on view e % K.
 * ``ClassifierTrainer``: one ``mmf_effcls_train_epoch`` and one ``mmf_effcls_eval`` call per epoch on the cached
   rows, a raw state dict on a strictly higher validation accuracy (:372-374), the best classifier put back into
@@ -23,7 +25,8 @@ Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a fro
 fine-tunes the whole backbone together with a 1538-d fusion head of another model class.  Further: the deployed
 ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; the flip comes from two
 cached views, and ColorJitter from ``jitter_views`` cached views (0 by default: none; K = epochs gives every image a
-fresh draw in every epoch, as the script's DataLoader does); fp32, no autocast / GradScaler; a seeded generator
+fresh draw in every epoch, as the script's DataLoader does), RandomJPEGCompression -- which the script does not apply,
+the reference's dataset transform does -- from ``jpeg_views``; fp32, no autocast / GradScaler; a seeded generator
 instead of the global RNG; file names sorted before the seeded shuffle (os.listdir order is arbitrary); unreadable
 images dropped instead of fed as a blank tensor.
 """
@@ -120,7 +123,33 @@ def jitter_params(N: int, views: int, seed: int, brightness: float = 0.2, contra
     return ops, factors, hue_shift
 
 
-def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None):
+def jpeg_params(N: int, views: int, seed: int, quality_range=(40, 80)) -> np.ndarray:
+    """RandomJPEGCompression's draw for ``views`` views of N images -> int32 [views, N], the ``quality`` of
+    ``Engine.jpeg_compress`` per view: uniform on the closed range, as the reference's ``random.randint(lo, hi)``.
+    From a ``torch.Generator`` of its own, seeded by ``seed`` alone: ``jitter_params`` with the same seed draws what it
+    drew without.  ValueError for a range outside 1..100 or reversed."""
+    try:
+        lo, hi = (int(v) for v in quality_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"jpeg_params: quality_range must be (lo, hi), got {quality_range!r}") from None
+    if not 1 <= lo <= hi <= 100:
+        raise ValueError(f"jpeg_params: quality_range must satisfy 1 <= lo <= hi <= 100, got ({lo}, {hi})")
+    if int(views) < 0 or int(N) < 0:
+        raise ValueError(f"jpeg_params: N and views must be >= 0, got {N}, {views}")
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.randint(lo, hi + 1, (int(views), int(N)), generator=g).numpy().astype(np.int32)
+
+
+def _jpeg_arg(jpeg, N: int) -> np.ndarray:
+    q = np.asarray(jpeg)
+    if q.ndim != 2 or q.shape[1] != N or q.shape[0] < 1 or q.dtype.kind not in "iu":
+        raise ValueError(f"jpeg: expected int qualities [K, {N}], K >= 1, got {q.shape} {q.dtype}")
+    if q.size and (q.min() < 1 or q.max() > 100):
+        raise ValueError(f"jpeg: qualities must be in 1..100, got {q.min()}..{q.max()}")
+    return q.astype(np.int32)
+
+
+def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None, jpeg=None):
     """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
     the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
     staged as analyze_pairs stages them (device JPEG decode where it applies, Pillow otherwise, the Pillow-exact
@@ -130,16 +159,30 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
     ``jitter`` = (ops, factors, hue_shift) of ``jitter_params(N, views, ...)``: the rows become float32
     [views, N, 1280] (both of them with ``flip``), view v being the staged window after ``Engine.color_jitter``
     with draw v.  Every operation is per pixel or a whole-image mean, so jitter and flip commute exactly: the
-    mirrored view is the mirror of the jittered window."""
+    mirrored view is the mirror of the jittered window.  That holds for jitter only.
+
+    ``jpeg`` = the int qualities [K, N] of ``jpeg_params(N, K, ...)``: view v is ``Engine.jpeg_compress`` of the
+    window at jpeg[v] -- of the jittered window where ``jitter`` is given too, the reference's order (its K must be
+    the same: ValueError otherwise).  The JPEG round trip does NOT commute with the mirror: the bias of the chroma
+    downsampling alternates with the column's parity, and so does the upsampling's.  So with ``flip`` the mirrored
+    row is that of ``jpeg_compress(hflip(window))``, mirrored first and compressed after as in the reference's
+    Compose, not that of the mirrored compressed window."""
     paths = list(image_paths)
     N = len(paths)
+    if jpeg is not None:
+        jpeg = _jpeg_arg(jpeg, N)
     if jitter is not None:
         j_ops, j_fac, j_hue = (np.asarray(a) for a in jitter)
         views = j_ops.shape[0]
         if j_ops.shape != (views, N, 4) or j_fac.shape != (views, N, 3) or j_hue.shape != (views, N) or views < 1:
             raise ValueError(f"jitter: expected ops [K, {N}, 4], factors [K, {N}, 3], hue_shift [K, {N}], K >= 1, got "
                              f"{j_ops.shape}, {j_fac.shape}, {j_hue.shape}")
-    shape = (N, WIDTH) if jitter is None else (views, N, WIDTH)
+        if jpeg is not None and jpeg.shape[0] != views:
+            raise ValueError(f"jitter has {views} views and jpeg {jpeg.shape[0]}: they must agree")
+    elif jpeg is not None:
+        views = jpeg.shape[0]
+    plain = jitter is None and jpeg is None
+    shape = (N, WIDTH) if plain else (views, N, WIDTH)
     feats = np.zeros(shape, np.float32)
     flipped = np.zeros(shape, np.float32) if flip else None
     ok = np.ones(N, bool)
@@ -166,16 +209,21 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
         a, b, rgb = staged
         eff, _ = forensics._windows(*rgb)
         eng = forensics.engine
-        if jitter is None:
+        if plain:
             feats[a:b] = eng.effnet_pooled(eff).cpu().numpy()
             if flip:
                 flipped[a:b] = eng.effnet_pooled(eng.hflip(eff)).cpu().numpy()
             return
         for v in range(views):
-            win = eng.color_jitter(eff, j_ops[v, a:b], j_fac[v, a:b], j_hue[v, a:b])
+            win = eff if jitter is None else eng.color_jitter(eff, j_ops[v, a:b], j_fac[v, a:b], j_hue[v, a:b])
+            mirrored = eng.hflip(win) if flip else None
+            if jpeg is not None:
+                win = eng.jpeg_compress(win, jpeg[v, a:b])
+                if flip:
+                    mirrored = eng.jpeg_compress(mirrored, jpeg[v, a:b])
             feats[v, a:b] = eng.effnet_pooled(win).cpu().numpy()
             if flip:
-                flipped[v, a:b] = eng.effnet_pooled(eng.hflip(win)).cpu().numpy()
+                flipped[v, a:b] = eng.effnet_pooled(mirrored).cpu().numpy()
 
     if chunks:
         forensics._run_chunks(chunks, host_stage, device_part)
@@ -331,11 +379,22 @@ class ClassifierTrainer:
 def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epochs: int = 10,
                  sample_per_label: int = 2500, forensics=None, checkpoint_path: Optional[str] = DEFAULT_FILE, *,
                  device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False,
-                 jitter_views: int = 0):
+                 jitter_views: int = 0, jpeg_views: int = 0, jpeg_quality=(40, 80)):
     """train_cifake_forensics.py:276-379: the CIFAKE tree's balanced sample and split, one feature extraction per
     split (two views of the training images with ``flip``; with ``jitter_views`` = K, K colour-jittered draws of
-    each, from ``jitter_params(N, K, seed)``), unreadable images dropped and counted, then the trainer.  Returns the
-    history."""
+    each, from ``jitter_params(N, K, seed)``; with ``jpeg_views`` = K, K views saved as JPEGs at a quality drawn
+    from the closed range ``jpeg_quality`` and loaded back, ``jpeg_params(N, K, seed, jpeg_quality)`` -- where both are
+    non-zero they must be equal, and view v is jittered first and compressed after), unreadable images dropped and
+    counted, then the trainer.  Returns the history."""
+    jitter_views, jpeg_views = int(jitter_views), int(jpeg_views)
+    if jitter_views < 0 or jpeg_views < 0:
+        raise ValueError(f"jitter_views and jpeg_views must be >= 0, got {jitter_views}, {jpeg_views}")
+    if jitter_views and jpeg_views and jitter_views != jpeg_views:
+        raise ValueError(f"jitter_views={jitter_views} and jpeg_views={jpeg_views}: where both are set they must be "
+                         f"equal")
+    if jpeg_views:
+        jpeg_params(0, 0, seed, jpeg_quality)  # the range checked before any file is read
+    views = jitter_views or jpeg_views
     tr_p, tr_y, va_p, va_y = load_cifake_data(cifake_root, sample_per_label)
     print(f"Loaded {len(tr_p)} training samples ({tr_y.count(0)} REAL, {tr_y.count(1)} FAKE)")
     print(f"Loaded {len(va_p)} validation samples ({va_y.count(0)} REAL, {va_y.count(1)} FAKE)")
@@ -343,7 +402,8 @@ def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epoch
         from .api import MisinfoForensics
         forensics = MisinfoForensics(device=device)
     jitter = jitter_params(len(tr_p), jitter_views, seed) if jitter_views else None
-    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter)
+    jpeg = jpeg_params(len(tr_p), jpeg_views, seed, jpeg_quality) if jpeg_views else None
+    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter, jpeg=jpeg)
     ok_t = out[-1]
     xv, ok_v = extract_image_features(forensics, va_p)
     dropped = int((~ok_t).sum() + (~ok_v).sum())
@@ -352,7 +412,7 @@ def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epoch
     tr_y, va_y = np.asarray(tr_y)[ok_t], np.asarray(va_y)[ok_v]
     train = (out[0][..., ok_t, :], out[1][..., ok_t, :]) if flip else out[0][..., ok_t, :]
     trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip,
-                                jitter_views=jitter_views)
+                                jitter_views=views)
     history = trainer.fit(train, tr_y, xv[ok_v], va_y, checkpoint_path=checkpoint_path,
                           save_full_model=save_full_model)
     for h in history:
@@ -374,10 +434,16 @@ def main(argv=None) -> None:
     ap.add_argument("--jitter-views", type=int, default=0, metavar="K",
                     help="ColorJitter(0.2, 0.2, 0.2, 0.1): K cached draws per image, epoch e trains on draw e %% K "
                          "(0: none; the number of epochs: a fresh draw per image and epoch, as the script)")
+    ap.add_argument("--jpeg-views", type=int, default=0, metavar="K",
+                    help="RandomJPEGCompression: K cached views per image saved as JPEGs and loaded back (0: none; "
+                         "with --jitter-views the same K: jittered first, compressed after)")
+    ap.add_argument("--jpeg-quality", type=int, nargs=2, default=(40, 80), metavar=("LO", "HI"),
+                    help="the closed range the JPEG quality is drawn from")
     ap.add_argument("--checkpoint", default=DEFAULT_FILE)
     a = ap.parse_args(argv)
     train_cifake(a.root, batch_size=a.batch_size, lr=a.lr, epochs=a.epochs, sample_per_label=a.samples_per_label,
-                 checkpoint_path=a.checkpoint, flip=not a.no_flip, jitter_views=a.jitter_views)
+                 checkpoint_path=a.checkpoint, flip=not a.no_flip, jitter_views=a.jitter_views, jpeg_views=a.jpeg_views,
+                 jpeg_quality=tuple(a.jpeg_quality))
 
 
 if __name__ == "__main__":

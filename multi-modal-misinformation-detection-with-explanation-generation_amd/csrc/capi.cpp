@@ -843,6 +843,21 @@ int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, c
   return 0;
 }
 
+int64_t mmf_jpeg_roundtrip_ws_bytes(int H, int W) { return (int64_t)jpeg_roundtrip_ws_bytes(H, W); }
+
+int mmf_jpeg_roundtrip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* quality, uint8_t* ws,
+                          int32_t* flags, void* stream) {
+  if (!src || !dst || !quality || !ws || !flags) return fail(MMF_EINVAL, "null argument");
+  if (B < 1 || B > kJpegEncMaxBatch || H < 1 || W < 1 || (double)H * W > (double)kJpegEncMaxPixels)
+    return fail(MMF_EINVAL, "jpeg_roundtrip_u8: bad shape (B=%d (1..%d) H=%d W=%d (H*W <= 2^30))", B, kJpegEncMaxBatch,
+                H, W);
+  if (dst == src) return fail(MMF_EINVAL, "jpeg_roundtrip_u8: dst must not be src");
+  if ((((uintptr_t)quality | (uintptr_t)flags) & 3) || ((uintptr_t)ws & 7))
+    return fail(MMF_EINVAL, "jpeg_roundtrip_u8: quality and flags must be 4-byte aligned, ws 8-byte");
+  HIPCHK(launch_jpeg_roundtrip_u8(src, dst, B, H, W, quality, ws, flags, (hipStream_t)stream));
+  return 0;
+}
+
 int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, const int32_t* perm, int N,
                            const uint64_t* keep, float p_drop, int batch, double lr, double beta1, double beta2,
                            double eps, double weight_decay, int step0, float* params, float* exp_avg,

@@ -228,6 +228,20 @@ constexpr int kJitterMaxBatch = 65535;               // the grid's y extent
 constexpr size_t kJitterMaxPixels = (size_t)1 << 40; // per image: 255 * pixels stays exact in a double (< 2^53)
 hipError_t launch_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops,
                                   const float* factors, const int32_t* hue_shift, uint64_t* ws, hipStream_t s);
+// A JPEG save-and-reload round trip on uint8 [B][H][W][3], byte-exact with Pillow (jpeg_encode.hip; include/mmf_hip.h
+// mmf_jpeg_roundtrip_u8): flags cleared, then two launches, grid (blocks or pixels, B); ws of
+// jpeg_roundtrip_ws_bytes(H, W) bytes per image (0 for a bad shape) holds the sample planes; hipErrorInvalidValue on
+// a bad shape with nothing launched
+constexpr int kJpegEncMaxBatch = 65535;                // the grid's y extent
+constexpr size_t kJpegEncMaxPixels = (size_t)1 << 30;  // per image: pixel and block indices stay ints
+size_t jpeg_roundtrip_ws_bytes(int H, int W);
+hipError_t launch_jpeg_roundtrip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* quality,
+                                    uint8_t* ws, int32_t* flags, hipStream_t s);
+// the round trip's block arithmetic on n raw level-shifted sample blocks [n][64] (|sample| <= 1024: the caller's
+// check) and one table of 64 bytes: quantised coefficients, range-limited samples, 1 where the block left the
+// exact range (mmf_jpeg_block_roundtrip_raw)
+hipError_t launch_jpeg_block_roundtrip(const int16_t* blocks, const uint8_t* table, int n, int16_t* coefs,
+                                       uint8_t* samples, int32_t* outside, hipStream_t s);
 // the CLS rows the text heads read: out fp32 [B][768] = x[b * row_stride ..]; a sequence with ovf[b] != 0 (nullable)
 // gets a NaN row, as launch_text_heads gives it NaN logits
 hipError_t launch_text_cls_rows(const float* x, int row_stride, const int* ovf, float* out, int B, hipStream_t s);

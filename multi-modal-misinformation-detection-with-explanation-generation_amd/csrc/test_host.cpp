@@ -433,6 +433,28 @@ int mmf_vault_topk_f32(const float* S, int B, int N, int k, float thresh, float*
   return test_launch_rc(launch_vault_topk(S, B, N, k, o, (hipStream_t)stream, ref), "vault_topk");
 }
 
+// the JPEG round trip's block arithmetic on raw sample blocks (jpeg_encode.hip; tests/test_gpu_jpeg_roundtrip.py).
+// The operands are read back and checked here first -- a synchronous call: 32-bit arithmetic holds for
+// |sample| <= 1024 and table entries 1..255
+int mmf_jpeg_block_roundtrip_raw(const int16_t* blocks, const uint8_t* table, int n, int16_t* coefs, uint8_t* samples,
+                                 int32_t* outside, void* stream) {
+  if (!blocks || !table || !coefs || !samples || !outside) return fail(MMF_EINVAL, "null argument");
+  if (n < 1 || n > (1 << 20)) return fail(MMF_EINVAL, "jpeg_block_roundtrip: n=%d (1..2^20)", n);
+  if (((uintptr_t)blocks | (uintptr_t)coefs) & 1 || (uintptr_t)outside & 3)
+    return fail(MMF_EINVAL, "jpeg_block_roundtrip: blocks and coefs must be 2-byte aligned, outside 4-byte");
+  std::vector<int16_t> host((size_t)n * 64);
+  uint8_t tab[64];
+  HIPCHK(hipMemcpyAsync(host.data(), blocks, host.size() * sizeof(int16_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(tab, table, sizeof(tab), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int16_t v : host)
+    if (v < -1024 || v > 1024) return fail(MMF_EINVAL, "jpeg_block_roundtrip: sample %d outside +-1024", (int)v);
+  for (uint8_t t : tab)
+    if (t == 0) return fail(MMF_EINVAL, "jpeg_block_roundtrip: a zero table entry");
+  return test_launch_rc(launch_jpeg_block_roundtrip(blocks, table, n, coefs, samples, outside, (hipStream_t)stream),
+                        "jpeg_block_roundtrip");
+}
+
 int mmf_vault_sort_cand_f32(const float* cs, const int32_t* cidx, int chunks, int chunk_rows, int B, int k,
                             float thresh, float* sims, int32_t* idx, float* disc, int disc_stride, const float* temb,
                             const float* title, int D, float* tsim, void* stream) {

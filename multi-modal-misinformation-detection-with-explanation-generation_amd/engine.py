@@ -312,6 +312,63 @@ class Engine:
                                            stream_ptr()), "mmf_color_jitter_u8")
         return out
 
+    def jpeg_compress(self, img, quality):
+        """The reference's RandomJPEGCompression at given qualities (misinformation_dataset.py:18-57) on staged uint8
+        [B, H, W, 3] windows (mmf_jpeg_roundtrip_u8), into a new device tensor: byte-equal to
+        ``Image.save(buf, format="JPEG", quality=q, optimize=False)``, reopen, ``convert("RGB")``.  ``quality``: an
+        int, or an int array of length B; 1..100, or 0 for an unchanged copy.  An image the kernel flags as outside
+        the decoder's exact range (none made from pixels has been seen to be) makes that round trip through Pillow
+        on the host."""
+        t = self._tensor(img)
+        if not (t.dtype == torch.uint8 and t.dim() == 4 and t.numel() > 0 and t.shape[3] == 3):
+            raise ValueError(f"jpeg_compress: expected a non-empty uint8 [B, H, W, 3] tensor, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+        t = t.to(self.device).contiguous()
+        B, H, Wd, _ = t.shape
+        q = np.asarray(quality)
+        if q.dtype.kind not in "iu" or q.ndim > 1:
+            raise ValueError(f"jpeg_compress: quality must be an int or an int array of length {B}")
+        q = np.broadcast_to(q, (B,)).astype(np.int32) if q.ndim == 0 else q.astype(np.int32)
+        if q.shape != (B,) or q.min() < 0 or q.max() > 100:
+            raise ValueError(f"jpeg_compress: quality must be {B} values in 0..100, got shape {q.shape}, "
+                             f"range {q.min() if q.size else None}..{q.max() if q.size else None}")
+        per_image = int(self.lib.mmf_jpeg_roundtrip_ws_bytes(H, Wd))
+        if per_image <= 0:
+            raise ValueError(f"jpeg_compress: unsupported image size {H} x {Wd}")
+        qd = torch.from_numpy(np.ascontiguousarray(q)).to(self.device)
+        out = torch.empty_like(t)
+        ws = torch.empty((B * per_image + 7) // 8, dtype=torch.int64, device=self.device)
+        flags = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.mmf_jpeg_roundtrip_u8(ptr(t), ptr(out), B, H, Wd, ptr(qd), ptr(ws), ptr(flags), stream_ptr()),
+              "mmf_jpeg_roundtrip_u8")
+        flagged = np.flatnonzero(self._jpeg_flags(flags))
+        if flagged.size:
+            self._jpeg_host_redo(t, out, q, flagged)
+        return out
+
+    @staticmethod
+    def _jpeg_flags(flags) -> np.ndarray:
+        """mmf_jpeg_roundtrip_u8's flags on the host (the call's one synchronisation)."""
+        return flags.cpu().numpy()
+
+    @staticmethod
+    def _jpeg_host_roundtrip(rgb: np.ndarray, quality: int) -> np.ndarray:
+        """uint8 [H, W, 3] saved as a JPEG and loaded back by Pillow, as the reference does it."""
+        import io
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(buf, format="JPEG", quality=int(quality), optimize=False)
+        buf.seek(0)
+        im = Image.open(buf)
+        im.load()
+        return np.asarray(im.convert("RGB"))
+
+    def _jpeg_host_redo(self, src, out, quality, flagged) -> None:
+        """The images the kernel declined: their round trip on the host, written over out[i]."""
+        for i in (int(v) for v in flagged):
+            done = self._jpeg_host_roundtrip(src[i].cpu().numpy(), int(quality[i]))
+            out[i].copy_(torch.from_numpy(np.array(done)))  # a copy: Pillow's buffer is read-only
+
     def clip_image(self, img):
         img = self._u8(img)
         e = self._f32(img.shape[0], 512)

@@ -36,6 +36,8 @@ SIGNATURES = {
     "mmf_effnet_pooled": (_I, [_P, _P, _I, _P, _P]),
     "mmf_hflip_u8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mmf_color_jitter_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mmf_jpeg_roundtrip_ws_bytes": (ctypes.c_int64, [_I, _I]),
+    "mmf_jpeg_roundtrip_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "mmf_effcls_train_epoch": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmf_effcls_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mmf_clip_image": (_I, [_P, _P, _I, _P, _P]),
@@ -134,6 +136,7 @@ SIGNATURES = {
     "mmf_vault_sims_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "mmf_vault_topk_f32": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P]),
     "mmf_vault_sort_cand_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "mmf_jpeg_block_roundtrip_raw": (_I, [_P, _P, _I, _P, _P, _P, _P]),
 }
 
 JITTER_CHUNKS = 256  # MMF_JITTER_CHUNKS: mmf_color_jitter_u8's ws is uint64 [B][JITTER_CHUNKS]
