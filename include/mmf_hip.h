@@ -172,6 +172,26 @@ int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, v
 int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops, const float* factors,
                         const int32_t* hue_shift, uint64_t* ws, void* stream);
 
+/* GaussianBlur on staged uint8 windows (misinformation_dataset.py:104-125: RandomApply([GaussianBlur(kernel_size=
+ * (5, 9), sigma=(0.1, 5.0))], p=0.3) between ColorJitter and RandomJPEGCompression), as torchvision's tensor
+ * backend computes it for a PIL image: float32 sums over a KY x KX window (KX the width) with reflected borders,
+ * the edge sample not repeated, rounded half to even.  src, dst uint8 [B][H][W][3]; dst and src must not overlap.
+ * No handle, no workspace; one ordinary launch on `stream`, no atomics.
+ *   weights fp32 [B][KY][KX]: image b's window, formed on the host (torch's own floats: the device evaluates no
+ *     exp).
+ *   apply int32 [B]: 0 copies image b unchanged (a RandomApply that did not fire), anything else blurs it.
+ * The order of the float32 operations is fixed: per output byte acc = 0, then for i = 0 .. KY - 1 (outer) and
+ * j = 0 .. KX - 1 (inner) acc = acc + w[i][j] * byte(y + i - KY/2, x + j - KX/2) with the product rounded before
+ * the add (no FMA), then rintf, a clamp to 0..255 (a NaN gives 0) and the byte.  torch's conv2d adds in another
+ * order, so a byte may differ from it by one where the exact sum is within float32 rounding of a half.
+ * (KX, KY) = (5, 9) has a kernel of its own; every other odd pair up to 15 runs with run-time tap counts, same
+ * arithmetic.  No value in the device arrays can make the kernel read or write out of bounds.  MMF_EINVAL with
+ * nothing launched and dst untouched: a NULL pointer, B outside 1..65535 (the grid), H or W < 1, H * W > 2^30
+ * (tile and byte indices), KX or KY even or outside 1..15, W <= KX/2 or H <= KY/2 (where torch's reflection pad
+ * raises), dst overlapping src anywhere (the byte ranges are compared), weights or apply not 4-byte aligned. */
+int mmf_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int KX, int KY, const float* weights,
+                         const int32_t* apply, void* stream);
+
 /* RandomJPEGCompression on staged uint8 windows (misinformation_dataset.py:18-57: the image saved as a JPEG at a
  * random quality and loaded back), byte-exact with Pillow's Image.save(format="JPEG", quality=q, optimize=False)
  * followed by Image.open(...).convert("RGB").  Huffman coding is lossless, so no bit stream is formed: libjpeg's

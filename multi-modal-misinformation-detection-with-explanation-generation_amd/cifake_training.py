@@ -13,7 +13,10 @@ and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads
   on the staged window, byte-exact with torchvision's PIL backend (``mmf_color_jitter_u8``), no window leaving the
   device.  With ``jpeg`` the rows of K views saved as JPEGs at given qualities and loaded back, the reference's
   RandomJPEGCompression (misinformation_dataset.py:18-57), byte-exact with Pillow (``mmf_jpeg_roundtrip_u8``).
+  With ``blur``, between those two, the reference's RandomApply([GaussianBlur((5, 9), (0.1, 5.0))], 0.3)
+  (misinformation_dataset.py:104-125) in torchvision's float32 arithmetic (``mmf_gaussian_blur_u8``).
 * ``jitter_params``: per view and image the order of the four operations, the three factors and the hue shift.
+* ``blur_params`` / ``gaussian_kernel2d``: per view and image whether the blur fires and its sigma; torch's weights.
 * ``jpeg_params``: per view and image the JPEG quality.
 * ``plan``: per epoch the permutation, the flip draws and the dropout masks; with views, epoch e trains on view e % K.
 * ``ClassifierTrainer``: one ``mmf_effcls_train_epoch`` and one ``mmf_effcls_eval`` call per epoch on the cached
@@ -25,10 +28,10 @@ Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a fro
 fine-tunes the whole backbone together with a 1538-d fusion head of another model class.  Further: the deployed
 ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; the flip comes from two
 cached views, and ColorJitter from ``jitter_views`` cached views (0 by default: none; K = epochs gives every image a
-fresh draw in every epoch, as the script's DataLoader does), RandomJPEGCompression -- which the script does not apply,
-the reference's dataset transform does -- from ``jpeg_views``; fp32, no autocast / GradScaler; a seeded generator
-instead of the global RNG; file names sorted before the seeded shuffle (os.listdir order is arbitrary); unreadable
-images dropped instead of fed as a blank tensor.
+fresh draw in every epoch, as the script's DataLoader does), GaussianBlur and RandomJPEGCompression -- which the
+script does not apply, the reference's dataset transform does -- from ``blur_views`` and ``jpeg_views``; fp32, no
+autocast / GradScaler; a seeded generator instead of the global RNG; file names sorted before the seeded shuffle
+(os.listdir order is arbitrary); unreadable images dropped instead of fed as a blank tensor.
 """
 from __future__ import annotations
 
@@ -140,6 +143,84 @@ def jpeg_params(N: int, views: int, seed: int, quality_range=(40, 80)) -> np.nda
     return torch.randint(lo, hi + 1, (int(views), int(N)), generator=g).numpy().astype(np.int32)
 
 
+BLUR_KERNEL_SIZE = (5, 9)  # the reference's GaussianBlur(kernel_size=(5, 9)): 5 wide, 9 high
+BLUR_MAX_TAPS = 15         # kBlurMaxTaps
+
+
+def _kernel_size(kernel_size, what: str) -> Tuple[int, int]:
+    try:
+        kx, ky = (int(v) for v in kernel_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: kernel_size must be (kx, ky), got {kernel_size!r}") from None
+    if not all(1 <= k <= BLUR_MAX_TAPS and k % 2 for k in (kx, ky)):
+        raise ValueError(f"{what}: kernel_size must be two odd numbers in 1..{BLUR_MAX_TAPS}, got ({kx}, {ky})")
+    return kx, ky
+
+
+def _kernel1d(k: int, sigma: float) -> torch.Tensor:
+    """torchvision's _get_gaussian_kernel1d, in its own torch CPU operations."""
+    lim = (k - 1) * 0.5
+    x = torch.linspace(-lim, lim, steps=k, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+def gaussian_kernel2d(sigma, kernel_size=BLUR_KERNEL_SIZE) -> np.ndarray:
+    """The weights of torchvision's GaussianBlur for one sigma (both axes) -> float32 [ky, kx], or for an array of
+    sigmas [...] -> [..., ky, kx]; ``kernel_size`` = (kx, ky), width first.  torchvision's own float32 operations on
+    the CPU (linspace, exp of -0.5 (x / sigma)^2, the division by the sum, the outer product by ``torch.mm``), so
+    the floats are torch's bit for bit and ``mmf_gaussian_blur_u8`` never evaluates an exp.  An array goes through
+    the one-sigma computation element by element: torch's vectorised exp need not round as its scalar one does, and
+    a window costs microseconds.  ValueError for a sigma that is not a positive finite number."""
+    kx, ky = _kernel_size(kernel_size, "gaussian_kernel2d")
+    s = np.asarray(sigma, dtype=np.float64)
+    if not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError(f"gaussian_kernel2d: sigma must be positive and finite, got {sigma!r}")
+    out = np.empty(s.shape + (ky, kx), np.float32)
+    flat = out.reshape(-1, ky, kx)
+    for n, v in enumerate(s.reshape(-1).tolist()):
+        flat[n] = torch.mm(_kernel1d(ky, v)[:, None], _kernel1d(kx, v)[None, :]).numpy()
+    return out
+
+
+def blur_params(N: int, views: int, seed: int, p: float = 0.3, sigma=(0.1, 5.0)):
+    """RandomApply([GaussianBlur(sigma=(lo, hi))], p)'s draws for ``views`` views of N images -> (apply bool
+    [views, N], sigma float32 [views, N]), the ``apply`` and ``sigma`` of ``Engine.gaussian_blur`` per view.  From a
+    ``torch.Generator`` of its own, seeded by ``seed`` alone, in this order: ``torch.rand(views, N) <= p`` as
+    RandomApply tests it (torchvision skips when ``p < torch.rand(1)``), then the sigmas as GaussianBlur.get_params'
+    ``torch.empty(...).uniform_(lo, hi)`` in float32 -- drawn for every image, applied or not, so the draws do not
+    depend on p.  ``jitter_params`` and ``jpeg_params`` with the same seed draw what they drew without.  ValueError
+    for p outside [0, 1] or a range that is not 0 < lo <= hi."""
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"blur_params: p must be in [0, 1], got {p}")
+    try:
+        lo, hi = (float(v) for v in sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"blur_params: sigma must be (lo, hi), got {sigma!r}") from None
+    if not 0.0 < lo <= hi < float("inf"):
+        raise ValueError(f"blur_params: sigma must satisfy 0 < lo <= hi, got ({lo}, {hi})")
+    if int(views) < 0 or int(N) < 0:
+        raise ValueError(f"blur_params: N and views must be >= 0, got {N}, {views}")
+    g = torch.Generator().manual_seed(int(seed))
+    apply = (torch.rand(int(views), int(N), generator=g) <= float(p)).numpy()
+    s = torch.empty(int(views), int(N), dtype=torch.float32).uniform_(lo, hi, generator=g).numpy()
+    return apply, s
+
+
+def _blur_arg(blur, N: int):
+    try:
+        apply, sigma = (np.asarray(a) for a in blur)
+    except (TypeError, ValueError):
+        raise ValueError("blur: expected (apply, sigma)") from None
+    if (apply.ndim != 2 or apply.shape[1] != N or apply.shape[0] < 1 or sigma.shape != apply.shape
+            or apply.dtype != np.bool_ or sigma.dtype.kind != "f"):
+        raise ValueError(f"blur: expected apply bool [K, {N}] and sigma float [K, {N}], K >= 1, got {apply.shape} "
+                         f"{apply.dtype}, {sigma.shape} {sigma.dtype}")
+    if sigma.size and not (np.isfinite(sigma).all() and (sigma > 0).all()):
+        raise ValueError("blur: every sigma must be positive and finite")
+    return apply, sigma.astype(np.float32)
+
+
 def _jpeg_arg(jpeg, N: int) -> np.ndarray:
     q = np.asarray(jpeg)
     if q.ndim != 2 or q.shape[1] != N or q.shape[0] < 1 or q.dtype.kind not in "iu":
@@ -149,7 +230,7 @@ def _jpeg_arg(jpeg, N: int) -> np.ndarray:
     return q.astype(np.int32)
 
 
-def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None, jpeg=None):
+def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None, jpeg=None, blur=None):
     """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
     the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
     staged as analyze_pairs stages them (device JPEG decode where it applies, Pillow otherwise, the Pillow-exact
@@ -166,22 +247,36 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
     the same: ValueError otherwise).  The JPEG round trip does NOT commute with the mirror: the bias of the chroma
     downsampling alternates with the column's parity, and so does the upsampling's.  So with ``flip`` the mirrored
     row is that of ``jpeg_compress(hflip(window))``, mirrored first and compressed after as in the reference's
-    Compose, not that of the mirrored compressed window."""
+    Compose, not that of the mirrored compressed window.
+
+    ``blur`` = (apply bool [K, N], sigma float [K, N]) of ``blur_params(N, K, ...)``: view v passes through
+    ``Engine.gaussian_blur`` with draw v between the jitter and the JPEG round trip, the Compose's order (K must
+    agree with the other two where they are given: ValueError otherwise).  The blur does not commute with the mirror
+    bit for bit either: its taps are added left to right in a fixed order, and a float32 sum taken in the opposite
+    order can round to the other side at a tie.  So with ``flip`` the mirrored row is that of
+    ``gaussian_blur(hflip(window))``, mirrored first and blurred after, and the JPEG round trip follows."""
     paths = list(image_paths)
     N = len(paths)
     if jpeg is not None:
         jpeg = _jpeg_arg(jpeg, N)
+    if blur is not None:
+        b_apply, b_sigma = _blur_arg(blur, N)
+    counts = {}  # the K of each step that is given
     if jitter is not None:
         j_ops, j_fac, j_hue = (np.asarray(a) for a in jitter)
         views = j_ops.shape[0]
         if j_ops.shape != (views, N, 4) or j_fac.shape != (views, N, 3) or j_hue.shape != (views, N) or views < 1:
             raise ValueError(f"jitter: expected ops [K, {N}, 4], factors [K, {N}, 3], hue_shift [K, {N}], K >= 1, got "
                              f"{j_ops.shape}, {j_fac.shape}, {j_hue.shape}")
-        if jpeg is not None and jpeg.shape[0] != views:
-            raise ValueError(f"jitter has {views} views and jpeg {jpeg.shape[0]}: they must agree")
-    elif jpeg is not None:
-        views = jpeg.shape[0]
-    plain = jitter is None and jpeg is None
+        counts["jitter"] = views
+    if blur is not None:
+        counts["blur"] = b_apply.shape[0]
+    if jpeg is not None:
+        counts["jpeg"] = jpeg.shape[0]
+    if len(set(counts.values())) > 1:
+        raise ValueError(" and ".join(f"{name} has {k} views" for name, k in counts.items()) + ": they must agree")
+    plain = not counts
+    views = 0 if plain else next(iter(counts.values()))
     shape = (N, WIDTH) if plain else (views, N, WIDTH)
     feats = np.zeros(shape, np.float32)
     flipped = np.zeros(shape, np.float32) if flip else None
@@ -205,6 +300,15 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
                     ok[a + i] = False
             return a, b, forensics._stage_images(pils)
 
+    def after_flip(eng, x, v, a, b):
+        """What follows the flip in the Compose for view v of images a .. b - 1 -- the blur, the JPEG round trip --
+        and the tower."""
+        if blur is not None:
+            x = eng.gaussian_blur(x, b_sigma[v, a:b], b_apply[v, a:b])
+        if jpeg is not None:
+            x = eng.jpeg_compress(x, jpeg[v, a:b])
+        return eng.effnet_pooled(x).cpu().numpy()
+
     def device_part(staged):
         a, b, rgb = staged
         eff, _ = forensics._windows(*rgb)
@@ -216,14 +320,9 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
             return
         for v in range(views):
             win = eff if jitter is None else eng.color_jitter(eff, j_ops[v, a:b], j_fac[v, a:b], j_hue[v, a:b])
-            mirrored = eng.hflip(win) if flip else None
-            if jpeg is not None:
-                win = eng.jpeg_compress(win, jpeg[v, a:b])
-                if flip:
-                    mirrored = eng.jpeg_compress(mirrored, jpeg[v, a:b])
-            feats[v, a:b] = eng.effnet_pooled(win).cpu().numpy()
+            feats[v, a:b] = after_flip(eng, win, v, a, b)
             if flip:
-                flipped[v, a:b] = eng.effnet_pooled(mirrored).cpu().numpy()
+                flipped[v, a:b] = after_flip(eng, eng.hflip(win), v, a, b)
 
     if chunks:
         forensics._run_chunks(chunks, host_stage, device_part)
@@ -379,22 +478,28 @@ class ClassifierTrainer:
 def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epochs: int = 10,
                  sample_per_label: int = 2500, forensics=None, checkpoint_path: Optional[str] = DEFAULT_FILE, *,
                  device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False,
-                 jitter_views: int = 0, jpeg_views: int = 0, jpeg_quality=(40, 80)):
+                 jitter_views: int = 0, jpeg_views: int = 0, jpeg_quality=(40, 80), blur_views: int = 0,
+                 blur_p: float = 0.3, blur_sigma=(0.1, 5.0)):
     """train_cifake_forensics.py:276-379: the CIFAKE tree's balanced sample and split, one feature extraction per
     split (two views of the training images with ``flip``; with ``jitter_views`` = K, K colour-jittered draws of
-    each, from ``jitter_params(N, K, seed)``; with ``jpeg_views`` = K, K views saved as JPEGs at a quality drawn
-    from the closed range ``jpeg_quality`` and loaded back, ``jpeg_params(N, K, seed, jpeg_quality)`` -- where both are
-    non-zero they must be equal, and view v is jittered first and compressed after), unreadable images dropped and
-    counted, then the trainer.  Returns the history."""
-    jitter_views, jpeg_views = int(jitter_views), int(jpeg_views)
-    if jitter_views < 0 or jpeg_views < 0:
-        raise ValueError(f"jitter_views and jpeg_views must be >= 0, got {jitter_views}, {jpeg_views}")
-    if jitter_views and jpeg_views and jitter_views != jpeg_views:
-        raise ValueError(f"jitter_views={jitter_views} and jpeg_views={jpeg_views}: where both are set they must be "
-                         f"equal")
+    each, from ``jitter_params(N, K, seed)``; with ``blur_views`` = K, K views blurred with probability ``blur_p``
+    at a sigma drawn from ``blur_sigma``, ``blur_params(N, K, seed, blur_p, blur_sigma)``; with ``jpeg_views`` = K,
+    K views saved as JPEGs at a quality drawn from the closed range ``jpeg_quality`` and loaded back,
+    ``jpeg_params(N, K, seed, jpeg_quality)`` -- the ones that are non-zero must be equal, and view v is jittered
+    first, blurred next and compressed last, the order of the reference dataset's Compose), unreadable images
+    dropped and counted, then the trainer.  Returns the history."""
+    jitter_views, blur_views, jpeg_views = int(jitter_views), int(blur_views), int(jpeg_views)
+    if jitter_views < 0 or blur_views < 0 or jpeg_views < 0:
+        raise ValueError(f"jitter_views, blur_views and jpeg_views must be >= 0, got {jitter_views}, {blur_views}, "
+                         f"{jpeg_views}")
+    if len({k for k in (jitter_views, blur_views, jpeg_views) if k}) > 1:
+        raise ValueError(f"jitter_views={jitter_views}, blur_views={blur_views} and jpeg_views={jpeg_views}: the ones "
+                         f"that are set must be equal")
     if jpeg_views:
         jpeg_params(0, 0, seed, jpeg_quality)  # the range checked before any file is read
-    views = jitter_views or jpeg_views
+    if blur_views:
+        blur_params(0, 0, seed, blur_p, blur_sigma)
+    views = jitter_views or blur_views or jpeg_views
     tr_p, tr_y, va_p, va_y = load_cifake_data(cifake_root, sample_per_label)
     print(f"Loaded {len(tr_p)} training samples ({tr_y.count(0)} REAL, {tr_y.count(1)} FAKE)")
     print(f"Loaded {len(va_p)} validation samples ({va_y.count(0)} REAL, {va_y.count(1)} FAKE)")
@@ -403,7 +508,8 @@ def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epoch
         forensics = MisinfoForensics(device=device)
     jitter = jitter_params(len(tr_p), jitter_views, seed) if jitter_views else None
     jpeg = jpeg_params(len(tr_p), jpeg_views, seed, jpeg_quality) if jpeg_views else None
-    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter, jpeg=jpeg)
+    blur = blur_params(len(tr_p), blur_views, seed, blur_p, blur_sigma) if blur_views else None
+    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter, jpeg=jpeg, blur=blur)
     ok_t = out[-1]
     xv, ok_v = extract_image_features(forensics, va_p)
     dropped = int((~ok_t).sum() + (~ok_v).sum())
@@ -434,6 +540,12 @@ def main(argv=None) -> None:
     ap.add_argument("--jitter-views", type=int, default=0, metavar="K",
                     help="ColorJitter(0.2, 0.2, 0.2, 0.1): K cached draws per image, epoch e trains on draw e %% K "
                          "(0: none; the number of epochs: a fresh draw per image and epoch, as the script)")
+    ap.add_argument("--blur-views", type=int, default=0, metavar="K",
+                    help="RandomApply([GaussianBlur((5, 9), sigma)], p): K cached views per image (0: none; the same "
+                         "K as --jitter-views / --jpeg-views where those are set: after the jitter, before the JPEG)")
+    ap.add_argument("--blur-p", type=float, default=0.3, metavar="P", help="the probability that a view is blurred")
+    ap.add_argument("--blur-sigma", type=float, nargs=2, default=(0.1, 5.0), metavar=("LO", "HI"),
+                    help="the range the blur's sigma is drawn from")
     ap.add_argument("--jpeg-views", type=int, default=0, metavar="K",
                     help="RandomJPEGCompression: K cached views per image saved as JPEGs and loaded back (0: none; "
                          "with --jitter-views the same K: jittered first, compressed after)")
@@ -443,7 +555,8 @@ def main(argv=None) -> None:
     a = ap.parse_args(argv)
     train_cifake(a.root, batch_size=a.batch_size, lr=a.lr, epochs=a.epochs, sample_per_label=a.samples_per_label,
                  checkpoint_path=a.checkpoint, flip=not a.no_flip, jitter_views=a.jitter_views, jpeg_views=a.jpeg_views,
-                 jpeg_quality=tuple(a.jpeg_quality))
+                 jpeg_quality=tuple(a.jpeg_quality), blur_views=a.blur_views, blur_p=a.blur_p,
+                 blur_sigma=tuple(a.blur_sigma))
 
 
 if __name__ == "__main__":

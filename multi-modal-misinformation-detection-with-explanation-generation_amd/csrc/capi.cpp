@@ -843,6 +843,26 @@ int mmf_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, c
   return 0;
 }
 
+int mmf_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int KX, int KY, const float* weights,
+                         const int32_t* apply, void* stream) {
+  if (!src || !dst || !weights || !apply) return fail(MMF_EINVAL, "null argument");
+  if (B < 1 || B > kBlurMaxBatch || H < 1 || W < 1 || (double)H * W > (double)kBlurMaxPixels)
+    return fail(MMF_EINVAL, "gaussian_blur_u8: bad shape (B=%d (1..%d) H=%d W=%d (H*W <= 2^30))", B, kBlurMaxBatch, H, W);
+  if (KX < 1 || KY < 1 || KX > kBlurMaxTaps || KY > kBlurMaxTaps || !(KX & 1) || !(KY & 1))
+    return fail(MMF_EINVAL, "gaussian_blur_u8: KX=%d KY=%d must be odd, 1..%d", KX, KY, kBlurMaxTaps);
+  if (W <= KX / 2 || H <= KY / 2)
+    return fail(MMF_EINVAL, "gaussian_blur_u8: the reflection needs W=%d > KX/2=%d and H=%d > KY/2=%d", W, KX / 2, H,
+                KY / 2);
+  {  // a tile's halo reads rows that other workgroups write: any overlap, not only dst == src, would corrupt
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst, n = (uintptr_t)B * (uintptr_t)H * (uintptr_t)W * 3;
+    if (s0 < d0 + n && d0 < s0 + n) return fail(MMF_EINVAL, "gaussian_blur_u8: dst must not overlap src");
+  }
+  if (((uintptr_t)weights | (uintptr_t)apply) & 3)
+    return fail(MMF_EINVAL, "gaussian_blur_u8: weights and apply must be 4-byte aligned");
+  HIPCHK(launch_gaussian_blur_u8(src, dst, B, H, W, KX, KY, weights, apply, (hipStream_t)stream));
+  return 0;
+}
+
 int64_t mmf_jpeg_roundtrip_ws_bytes(int H, int W) { return (int64_t)jpeg_roundtrip_ws_bytes(H, W); }
 
 int mmf_jpeg_roundtrip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* quality, uint8_t* ws,

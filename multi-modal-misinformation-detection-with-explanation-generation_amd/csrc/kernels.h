@@ -228,6 +228,17 @@ constexpr int kJitterMaxBatch = 65535;               // the grid's y extent
 constexpr size_t kJitterMaxPixels = (size_t)1 << 40; // per image: 255 * pixels stays exact in a double (< 2^53)
 hipError_t launch_color_jitter_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ops,
                                   const float* factors, const int32_t* hue_shift, uint64_t* ws, hipStream_t s);
+// GaussianBlur on uint8 [B][H][W][3] with reflected borders (blur.hip; include/mmf_hip.h mmf_gaussian_blur_u8): one
+// launch, grid (tiles of kBlurTileRows rows x kBlurTileBytes row bytes, B), weights float32 [B][KY][KX], image b
+// copied where apply[b] == 0; (5, 9) compiled with constant taps, every other odd size up to kBlurMaxTaps with
+// run-time ones; hipErrorInvalidValue on a bad shape or size with nothing launched
+constexpr int kBlurTileRows = 32;
+constexpr int kBlurTileBytes = 256;                  // of a row's 3 * W
+constexpr int kBlurMaxTaps = 15;
+constexpr int kBlurMaxBatch = 65535;                 // the grid's y extent
+constexpr size_t kBlurMaxPixels = (size_t)1 << 30;   // per image: the tiles stay below 2^31, a row's bytes below 2^32
+hipError_t launch_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int KX, int KY,
+                                   const float* weights, const int32_t* apply, hipStream_t s);
 // A JPEG save-and-reload round trip on uint8 [B][H][W][3], byte-exact with Pillow (jpeg_encode.hip; include/mmf_hip.h
 // mmf_jpeg_roundtrip_u8): flags cleared, then two launches, grid (blocks or pixels, B); ws of
 // jpeg_roundtrip_ws_bytes(H, W) bytes per image (0 for a bad shape) holds the sample planes; hipErrorInvalidValue on

@@ -312,6 +312,43 @@ class Engine:
                                            stream_ptr()), "mmf_color_jitter_u8")
         return out
 
+    def gaussian_blur(self, img, sigma, apply=None, kernel_size=(5, 9)):
+        """torchvision's GaussianBlur on staged uint8 [B, H, W, 3] windows (mmf_gaussian_blur_u8), into a new device
+        tensor: float32 sums with reflected borders, rounded half to even, as its tensor backend computes them for
+        a PIL image -- in one fixed order of additions, so a byte can differ by one from torch's conv2d where the
+        exact sum is within float32 rounding of a half.  ``sigma``: a float, or an array of length B (both axes
+        share it); ``apply``: a bool array of length B, all True by default -- image b is copied unchanged where it
+        is False (a RandomApply that did not fire); ``kernel_size`` = (kx, ky), width first, odd, 1..15.  The
+        weights are torch's own, formed on the host (``cifake_training.gaussian_kernel2d``)."""
+        from .cifake_training import _kernel_size, gaussian_kernel2d
+        t = self._tensor(img)
+        if not (t.dtype == torch.uint8 and t.dim() == 4 and t.numel() > 0 and t.shape[3] == 3):
+            raise ValueError(f"gaussian_blur: expected a non-empty uint8 [B, H, W, 3] tensor, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+        t = t.to(self.device).contiguous()
+        B, H, Wd, _ = t.shape
+        kx, ky = _kernel_size(kernel_size, "gaussian_blur")
+        if Wd <= kx // 2 or H <= ky // 2:
+            raise ValueError(f"gaussian_blur: a {kx} x {ky} window reflects only in images wider than {kx // 2} and "
+                             f"higher than {ky // 2}, got {Wd} x {H}")
+        s = np.asarray(sigma, dtype=np.float64)
+        if s.ndim > 1 or (s.ndim == 1 and s.shape != (B,)):
+            raise ValueError(f"gaussian_blur: sigma must be a float or an array of length {B}, got shape {s.shape}")
+        s = np.broadcast_to(s, (B,))
+        if not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError("gaussian_blur: every sigma must be positive and finite")
+        on = np.ones(B, bool) if apply is None else np.asarray(apply)
+        if on.shape != (B,) or on.dtype != np.bool_:
+            raise ValueError(f"gaussian_blur: apply must be a bool array of length {B}, got {on.shape} {on.dtype}")
+        weights = np.zeros((B, ky, kx), np.float32)  # images that are copied read none
+        weights[on] = gaussian_kernel2d(s[on], (kx, ky))
+        wd = torch.from_numpy(weights).to(self.device)
+        ad = torch.from_numpy(on.astype(np.int32)).to(self.device)
+        out = torch.empty_like(t)
+        check(self.lib.mmf_gaussian_blur_u8(ptr(t), ptr(out), B, H, Wd, kx, ky, ptr(wd), ptr(ad), stream_ptr()),
+              "mmf_gaussian_blur_u8")
+        return out
+
     def jpeg_compress(self, img, quality):
         """The reference's RandomJPEGCompression at given qualities (misinformation_dataset.py:18-57) on staged uint8
         [B, H, W, 3] windows (mmf_jpeg_roundtrip_u8), into a new device tensor: byte-equal to

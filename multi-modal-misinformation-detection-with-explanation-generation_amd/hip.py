@@ -36,6 +36,7 @@ SIGNATURES = {
     "mmf_effnet_pooled": (_I, [_P, _P, _I, _P, _P]),
     "mmf_hflip_u8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mmf_color_jitter_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mmf_gaussian_blur_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mmf_jpeg_roundtrip_ws_bytes": (ctypes.c_int64, [_I, _I]),
     "mmf_jpeg_roundtrip_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "mmf_effcls_train_epoch": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
