@@ -144,6 +144,13 @@ int mmf_effnet_forward_f32(mmf_handle* h, const float* x, int B, float* logits, 
  * row, as it gives a non-finite score there. */
 int mmf_effnet_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, void* stream);
 
+/* The frozen part of the head-stage training (mmf_effhead_train_epoch below): the output of the last MBConv
+ * block, what the head conv features.8 reads.  img as mmf_effnet_pooled; trunk fp32 [B, 49, 320], 16-byte
+ * aligned: positions row-major over 7 x 7, channels innermost.  The launch sequence of the tower in use
+ * without the head GEMM, the pool and the classifier; the fp16 tower's values are converted to fp32 exactly,
+ * the fp32 tower's are copied.  Errors as mmf_effnet_pooled's. */
+int mmf_effnet_trunk(mmf_handle* h, const uint8_t* img, int B, float* trunk, void* stream);
+
 /* RandomHorizontalFlip's mirror on a staged uint8 window (train_cifake_forensics.py:39-45: Resize, then the
  * flip): dst[b][y][x][c] = src[b][y][W-1-x][c].  No handle.  dst and src must not overlap.  MMF_EINVAL with
  * nothing launched: a NULL pointer, a non-positive dimension, dst == src. */
@@ -249,6 +256,43 @@ int mmf_effcls_train_epoch(const float* feat, const int32_t* labels, int R, cons
  * batch's mean cross-entropy; row_logits fp32 [R][2].  Errors as the training call's. */
 int mmf_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, const float* params,
                     float* batch_loss, float* row_logits, void* stream);
+
+/* Training of EfficientNet's head conv stage -- features.8 = Conv2d(320, 1280, 1, bias=False) + BatchNorm2d(1280)
+ * + SiLU -- jointly with the classifier above, on cached trunk rows (mmf_effnet_trunk).  The BatchNorm runs in
+ * EVAL mode: its running statistics bn_mean / bn_var fp32 [1280] and bn_eps are inputs and never written, so a
+ * row does not depend on its minibatch (the script trains in model.train()).  Per minibatch of
+ * n <= 64 images, M = 49 n rows:
+ *   z = x W^T; s_c = gamma_c / sqrt(var_c + eps), t_c = beta_c - mean_c s_c; y = s_c z + t_c; a = y / (1 + exp(-y));
+ *   pooled[r][c] = (sum over the 49 positions, ascending) / 49; from here mmf_effcls_train_epoch's contract:
+ *   xd = pooled * keep * scale, logits, mean cross-entropy, torch.optim.Adam on ALL parameters (L2 decay added
+ *   to the gradient, bias correction by step0 + s + 1, constant lr).  Backward: dpooled = keep scale dl Wc,
+ *   dy = dpooled / 49 * sig (1 + y (1 - sig)), dgamma_c = sum dy (z - mean_c) / sqrt(var_c + eps), dbeta_c =
+ *   sum dy, dW[c][k] = sum (dy s_c) x[.][k]; no gradient with respect to the trunk.
+ * params, exp_avg, exp_avg_sq fp32 [MMF_EFFHEAD_PARAMS], state-dict order: features.8.0.weight [1280][320] |
+ * features.8.1.weight [1280] | features.8.1.bias [1280] | classifier.1.weight [2][1280] | classifier.1.bias [2].
+ * trunk fp32 [R][49][320]; labels, perm, keep, step_loss, step_correct, grad_out as mmf_effcls_train_epoch's (a
+ * perm entry outside [0, R) is clamped; keep is the mask on the POOLED row).  ws: mmf_effhead_ws_bytes(batch) bytes
+ * (host arithmetic; 0 for a batch outside 1..64), contents on entry do not matter.  No handle; three ordinary
+ * launches per minibatch on `stream`, no host synchronisation, no atomics.  All fp32; both contractions on the
+ * fp32-input MFMA, each output one fmaf chain in ascending order; every reduction has one fixed order
+ * (csrc/effhead_train.hip), so results are bit-reproducible and do not depend on how an epoch is split into calls.
+ * trunk, params, exp_avg, exp_avg_sq, grad_out and ws are 16-byte aligned, keep 8-byte, the rest 4-byte.
+ * MMF_EINVAL with nothing launched: what mmf_effcls_train_epoch rejects, a ws that is too small or misaligned, a
+ * bn_eps that is not finite and positive as the fp32 value the kernels use. */
+#define MMF_EFFHEAD_PARAMS 414722
+int64_t mmf_effhead_ws_bytes(int batch);
+int mmf_effhead_train_epoch(const float* trunk, const int32_t* labels, int R, const int32_t* perm, int N,
+                            const uint64_t* keep, float p_drop, int batch, const float* bn_mean, const float* bn_var,
+                            double bn_eps, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int step0, float* params, float* exp_avg, float* exp_avg_sq, float* step_loss,
+                            int32_t* step_correct, float* grad_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* validate on cached trunk rows: forward only, no dropout, consecutive batches of the R bank rows in file order,
+ * two launches per batch.  batch_loss fp32 [ceil(R / batch)], row_logits fp32 [R][2]; a row's logits do not depend
+ * on the batch size.  Errors as the training call's. */
+int mmf_effhead_eval(const float* trunk, const int32_t* labels, int R, int batch, const float* params,
+                     const float* bn_mean, const float* bn_var, double bn_eps, float* batch_loss, float* row_logits,
+                     void* ws, int64_t ws_bytes, void* stream);
 
 /* CLIP image embedding — get_image_features + L2 normalisation (misinfo_forensics.py:395-401,
  * 432-439).  img uint8 [B, 224, 224, 3] (CLIP-preprocessed geometry); emb fp32 [B, 512] unit. */

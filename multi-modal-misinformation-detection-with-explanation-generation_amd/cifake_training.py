@@ -22,9 +22,15 @@ and the file written is one ``MisinfoForensics(efficientnet_weights=...)`` loads
 * ``ClassifierTrainer``: one ``mmf_effcls_train_epoch`` and one ``mmf_effcls_eval`` call per epoch on the cached
   rows, a raw state dict on a strictly higher validation accuracy (:372-374), the best classifier put back into
   the detector.
+* ``HeadStageTrainer`` (``train_cifake(unfreeze="head")``): one stage deeper -- features.8, the 1x1 conv
+  320 -> 1280 with its BatchNorm's affine, trained jointly with the classifier (414,722 parameters) on cached trunk
+  rows [N, 49, 320] (``extract_image_features(level="trunk")``, ``Engine.effnet_trunk``) by
+  ``mmf_effhead_train_epoch`` / ``mmf_effhead_eval``.  The BatchNorm runs in eval mode, so a row does not depend on
+  its minibatch and the trunk can be cached; the 16 MBConv blocks stay frozen.
 * ``train_cifake`` / ``python -m mmf_amd.cifake_training``: the script's entry point.
 
-Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a frozen backbone, where the script
+Deviations, documented in DESIGN.md §7h.  The main one: a linear probe on a frozen backbone (with
+``unfreeze="head"``: the head conv stage and the classifier, BatchNorm in eval mode), where the script
 fine-tunes the whole backbone together with a 1538-d fusion head of another model class.  Further: the deployed
 ImageNet normalisation (misinfo_forensics.py:249-253), not the script's CLIP mean / std; the flip comes from two
 cached views, and ColorJitter from ``jitter_views`` cached views (0 by default: none; K = epochs gives every image a
@@ -45,6 +51,7 @@ import numpy as np
 import torch
 
 from . import io_utils
+from . import weights
 from . import training_common as TC
 from .training_common import _black, pack_keep  # pack_keep here: bool [N, 1280] -> uint64 [N, 20]
 
@@ -54,6 +61,10 @@ WIDTH = 1280
 WORDS = WIDTH // 64
 PARAM_KEYS = ("classifier.1.weight", "classifier.1.bias")
 N_PARAMS = 2 * WIDTH + 2  # MMF_EFFCLS_PARAMS
+TRUNK_CHANNELS, TRUNK_SHAPE = 320, (49, 320)  # what features.8 reads: 7 x 7 positions of 320 channels
+HEAD_PARAM_KEYS = ("features.8.0.weight", "features.8.1.weight", "features.8.1.bias") + PARAM_KEYS
+HEAD_N_PARAMS = WIDTH * TRUNK_CHANNELS + 2 * WIDTH + N_PARAMS  # MMF_EFFHEAD_PARAMS = 414722
+BN_EPS = weights.BN_EPS
 EXTENSIONS = (".jpg", ".jpeg", ".png")
 DEFAULT_FILE = "efficientnet_cifake_best.pth"
 
@@ -230,7 +241,8 @@ def _jpeg_arg(jpeg, N: int) -> np.ndarray:
     return q.astype(np.int32)
 
 
-def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None, jpeg=None, blur=None):
+def extract_image_features(forensics, image_paths: Sequence, flip: bool = False, jitter=None, jpeg=None, blur=None,
+                           level: str = "pooled"):
     """What the frozen backbone gives for every image -> (feats float32 [N, 1280], ok bool [N]), with ``flip`` also
     the rows of the mirrored windows: (feats, flipped float32 [N, 1280], ok).  In ``max_batch`` chunks: the images
     staged as analyze_pairs stages them (device JPEG decode where it applies, Pillow otherwise, the Pillow-exact
@@ -254,7 +266,19 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
     agree with the other two where they are given: ValueError otherwise).  The blur does not commute with the mirror
     bit for bit either: its taps are added left to right in a fixed order, and a float32 sum taken in the opposite
     order can round to the other side at a tie.  So with ``flip`` the mirrored row is that of
-    ``gaussian_blur(hflip(window))``, mirrored first and blurred after, and the JPEG round trip follows."""
+    ``gaussian_blur(hflip(window))``, mirrored first and blurred after, and the JPEG round trip follows.
+
+    ``level`` = "trunk": the rows ``HeadStageTrainer`` reads instead, the last MBConv block's output [.., N, 49, 320]
+    (``Engine.effnet_trunk``), through the same staging, flip, jitter, blur and JPEG path: only the final tower call
+    differs.  They come back as float32 TENSORS ON THE ENGINE'S DEVICE, filled chunk by chunk -- 62,720 bytes per view
+    and image, so 4,000 images x 2 flips x 10 views take 5.0 GB there -- and no more than one chunk of windows exists
+    at a time.  Both results are views of one allocation laid out as the trainer's bank, so ``HeadStageTrainer.fit``
+    trains on them in place; selecting rows out of them (an unreadable image dropped) makes a copy, and ``fit`` then
+    builds its bank as a second one: twice the size at the peak."""
+    if level not in ("pooled", "trunk"):
+        raise ValueError(f"level must be 'pooled' or 'trunk', got {level!r}")
+    trunk = level == "trunk"
+    row = TRUNK_SHAPE if trunk else (WIDTH,)
     paths = list(image_paths)
     N = len(paths)
     if jpeg is not None:
@@ -277,9 +301,17 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
         raise ValueError(" and ".join(f"{name} has {k} views" for name, k in counts.items()) + ": they must agree")
     plain = not counts
     views = 0 if plain else next(iter(counts.values()))
-    shape = (N, WIDTH) if plain else (views, N, WIDTH)
-    feats = np.zeros(shape, np.float32)
-    flipped = np.zeros(shape, np.float32) if flip else None
+    shape = ((N,) if plain else (views, N)) + row
+    if trunk:
+        # ONE allocation in plan()'s bank order -- per view its rows, then its mirrored rows -- of which the two
+        # results are views: HeadStageTrainer.fit recognises the layout and trains on it without a second copy
+        base = torch.zeros((max(views, 1), 2 if flip else 1, N) + row, dtype=torch.float32,
+                           device=forensics.engine.device)
+        feats = base[0, 0] if plain else base[:, 0]
+        flipped = (base[0, 1] if plain else base[:, 1]) if flip else None
+    else:
+        feats = np.zeros(shape, np.float32)
+        flipped = np.zeros(shape, np.float32) if flip else None
     ok = np.ones(N, bool)
     cap = forensics.engine.max_batch
     chunks = [(a, min(a + cap, N)) for a in range(0, N, cap)]
@@ -300,6 +332,9 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
                     ok[a + i] = False
             return a, b, forensics._stage_images(pils)
 
+    def tower(eng, x):
+        return eng.effnet_trunk(x) if trunk else eng.effnet_pooled(x).cpu().numpy()
+
     def after_flip(eng, x, v, a, b):
         """What follows the flip in the Compose for view v of images a .. b - 1 -- the blur, the JPEG round trip --
         and the tower."""
@@ -307,16 +342,16 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
             x = eng.gaussian_blur(x, b_sigma[v, a:b], b_apply[v, a:b])
         if jpeg is not None:
             x = eng.jpeg_compress(x, jpeg[v, a:b])
-        return eng.effnet_pooled(x).cpu().numpy()
+        return tower(eng, x)
 
     def device_part(staged):
         a, b, rgb = staged
         eff, _ = forensics._windows(*rgb)
         eng = forensics.engine
         if plain:
-            feats[a:b] = eng.effnet_pooled(eff).cpu().numpy()
+            feats[a:b] = tower(eng, eff)
             if flip:
-                flipped[a:b] = eng.effnet_pooled(eng.hflip(eff)).cpu().numpy()
+                flipped[a:b] = tower(eng, eng.hflip(eff))
             return
         for v in range(views):
             win = eff if jitter is None else eng.color_jitter(eff, j_ops[v, a:b], j_fac[v, a:b], j_hue[v, a:b])
@@ -326,9 +361,14 @@ def extract_image_features(forensics, image_paths: Sequence, flip: bool = False,
 
     if chunks:
         forensics._run_chunks(chunks, host_stage, device_part)
-    feats[..., ~ok, :] = 0
+    bad = np.flatnonzero(~ok)  # (an index list: the same statement for an array and for a device tensor)
+    for out in (feats, flipped):
+        if out is not None and len(bad):
+            if plain:
+                out[bad] = 0
+            else:
+                out[:, bad] = 0
     if flip:
-        flipped[..., ~ok, :] = 0
         return feats, flipped, ok
     return feats, ok
 
@@ -473,13 +513,135 @@ class ClassifierTrainer:
 
 
 # ---------------------------------------------------------------------------------------------
+# the head conv stage, trained with the classifier
+# ---------------------------------------------------------------------------------------------
+def _head_stage(detector):
+    stage = getattr(detector.efficientnet.features, "8")
+    return getattr(stage, "0"), getattr(stage, "1")
+
+
+def flatten_head_stage(detector) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(params float32 [414722], running_mean float32 [1280], running_var float32 [1280]) of the detector's
+    EfficientNet: features.8.0.weight | features.8.1.weight | features.8.1.bias | classifier.1.weight |
+    classifier.1.bias in state-dict order as one flat tensor, and the BatchNorm's statistics (copies)."""
+    conv, bn = _head_stage(detector)
+    lin = _classifier(detector)
+    flat = torch.cat([t.detach().reshape(-1).float() for t in (conv.weight, bn.weight, bn.bias, lin.weight, lin.bias)])
+    if flat.numel() != HEAD_N_PARAMS or tuple(conv.weight.shape[:2]) != (WIDTH, TRUNK_CHANNELS):
+        raise ValueError(f"a head stage of {flat.numel()} parameters, expected {HEAD_N_PARAMS}")
+    return flat, bn.running_mean.detach().float().clone(), bn.running_var.detach().float().clone()
+
+
+class HeadStageTrainer(ClassifierTrainer):
+    """ClassifierTrainer's loop one stage deeper: features.8 (the 1x1 conv and its BatchNorm's affine, in eval mode:
+    the running statistics are read, never updated) is trained jointly with the classifier on cached trunk rows
+    [.., N, 49, 320] (``extract_image_features(level="trunk")``), per epoch one ``mmf_effhead_train_epoch`` and one
+    ``mmf_effhead_eval`` call.  The bank stays on the device: 49 x 320 x 4 = 62,720 bytes per view and image, so
+    4,000 images x 2 flips x 10 views take 5.0 GB -- once, where the rows come from ``extract_image_features`` and
+    are passed on whole (``_bank``); twice at the peak where they had to be copied together.  The best parameters are kept on a strictly higher validation
+    accuracy; the checkpoint is a raw state dict of the five torchvision-named tensors."""
+
+    @staticmethod
+    def _data(feats, labels, what):
+        """Trunk rows float32 [N, 49, 320] (a numpy array or a tensor on any device) and labels [N] of 0 / 1 -> the
+        rows as a contiguous tensor, the labels int32."""
+        x = feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(np.asarray(feats, np.float32)))
+        y = np.asarray(labels)
+        if x.dim() != 3 or tuple(x.shape[1:]) != TRUNK_SHAPE or x.shape[0] < 1 or y.shape != (x.shape[0],):
+            raise ValueError(f"{what} trunk rows {tuple(x.shape)} / labels {y.shape} must be [N, 49, 320] / [N], N >= 1")
+        if x.dtype != torch.float32 or not bool(torch.isfinite(x).all()):
+            raise ValueError(f"{what} trunk rows must be finite float32")
+        if not np.isin(y, (0, 1)).all():
+            raise ValueError(f"{what} labels must be 0 / 1")
+        return x.contiguous(), y.astype(np.int32)
+
+    def fit(self, train, train_labels, val, val_labels, checkpoint_path: Optional[str] = None,
+            save_full_model: bool = False) -> List[dict]:
+        """``train``: trunk rows [N, 49, 320], or with ``flip`` the pair (rows, rows of the mirrored windows); with
+        ``jitter_views`` = K each of them [K, N, 49, 320], as ``extract_image_features(level="trunk")`` returns."""
+        f = self.forensics
+        eng, det = f.engine, f.detector
+        dev = eng.device
+        K = self.jitter_views
+        if self.flip and not (isinstance(train, (tuple, list)) and len(train) == 2):
+            raise ValueError("flip=True needs train = (trunk rows, trunk rows of the mirrored windows)")
+        parts = tuple(train) if self.flip else (train,)
+        if K and any(p.ndim != 4 or p.shape[0] != K for p in parts):
+            raise ValueError(f"jitter_views={K} needs training trunk rows [{K}, N, 49, 320], got "
+                             f"{[tuple(p.shape) for p in parts]}")
+        # the bank's blocks in plan()'s order: per view its rows, then (flip) its mirrored rows
+        blocks = [p[v] if K else p for v in range(max(K, 1)) for p in parts]
+        names = ("training", "mirrored training")
+        blocks = [self._data(x, train_labels, names[i % len(parts)]) for i, x in enumerate(blocks)]
+        yt = blocks[0][1]
+        bank = self._bank([x for x, _ in blocks], dev)
+        bank_labels = torch.from_numpy(np.concatenate([yt] * len(blocks))).to(dev)
+        xv, yv = self._data(val, val_labels, "validation")
+        xv, yv_d = xv.to(dev), torch.from_numpy(yv).to(dev)
+        N, bs = len(yt), self.batch_size
+        params, mean, var = (t.to(dev).contiguous() for t in flatten_head_stage(det))
+        m, v = torch.zeros_like(params), torch.zeros_like(params)
+        spe = -(-N // bs)
+        history, best_acc, best, step0 = [], 0.0, None, 0
+        for epoch, (perm, keep, _) in enumerate(plan(N, bs, self.epochs, self.seed, self.flip, K), 1):
+            sl, sc = eng.effhead_train_epoch(bank, bank_labels, torch.from_numpy(perm).to(dev),
+                                             torch.from_numpy(keep.view(np.int64)).to(dev), P_DROP, bs, mean, var,
+                                             BN_EPS, self.lr, BETAS, EPS, self.weight_decay, step0, params, m, v)
+            bl, lg = eng.effhead_eval(xv, yv_d, bs, params, mean, var, BN_EPS)
+            step0 += spe
+            train_loss, train_acc, val_loss, val_acc, _ = TC.classifier_epoch_metrics(epoch, sl, sc, bl, lg, N, yv)
+            history.append({"epoch": epoch, "train_loss": train_loss, "train_acc": train_acc, "val_loss": val_loss,
+                            "val_acc": val_acc})
+            if val_acc > best_acc:
+                best_acc, best = val_acc, params.clone()
+                if checkpoint_path:
+                    torch.save(self._state(best, save_full_model), checkpoint_path)
+        self.best_val_acc = best_acc
+        self._install(best if best is not None else params)
+        return history
+
+    @staticmethod
+    def _bank(blocks, dev) -> torch.Tensor:
+        """The blocks [N, 49, 320] as one bank [len(blocks) N, 49, 320] on the device.  Blocks that already lie there
+        one behind the other in one allocation (what ``extract_image_features(level="trunk")`` returns) are taken as
+        they are; anything else is copied together, the bank then existing beside the caller's tensors."""
+        first, n = blocks[0], blocks[0].numel() * 4
+        if first.device == dev and all(b.device == dev and b.untyped_storage().data_ptr() ==
+                                       first.untyped_storage().data_ptr() and b.data_ptr() == first.data_ptr() + i * n
+                                       for i, b in enumerate(blocks)):
+            return torch.as_strided(first, (len(blocks) * first.shape[0],) + TRUNK_SHAPE, (49 * 320, 320, 1))
+        return blocks[0].to(dev) if len(blocks) == 1 else torch.cat([b.to(dev) for b in blocks])
+
+    def _tensors(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        flat = flat.detach().cpu()
+        shapes = ((WIDTH, TRUNK_CHANNELS, 1, 1), (WIDTH,), (WIDTH,), (2, WIDTH), (2,))
+        out, o = {}, 0
+        for key, shape in zip(HEAD_PARAM_KEYS, shapes):
+            n = int(np.prod(shape))
+            out[key] = flat[o:o + n].reshape(shape).clone()
+            o += n
+        return out
+
+    def _install(self, flat: torch.Tensor) -> None:
+        """In-place copies, then ONE detector.sync: it re-folds the BatchNorm into the fp16 and fp32 head weights and
+        re-runs check_effnet_precision on the new stage."""
+        det = self.forensics.detector
+        conv, bn = _head_stage(det)
+        lin, t = _classifier(det), self._tensors(flat)
+        with torch.no_grad():
+            for dst, key in zip((conv.weight, bn.weight, bn.bias, lin.weight, lin.bias), HEAD_PARAM_KEYS):
+                dst.copy_(t[key])
+        det.sync(("effnet",))
+
+
+# ---------------------------------------------------------------------------------------------
 # the script's entry point
 # ---------------------------------------------------------------------------------------------
 def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epochs: int = 10,
                  sample_per_label: int = 2500, forensics=None, checkpoint_path: Optional[str] = DEFAULT_FILE, *,
                  device: str = "cuda", seed: int = 0, flip: bool = True, save_full_model: bool = False,
                  jitter_views: int = 0, jpeg_views: int = 0, jpeg_quality=(40, 80), blur_views: int = 0,
-                 blur_p: float = 0.3, blur_sigma=(0.1, 5.0)):
+                 blur_p: float = 0.3, blur_sigma=(0.1, 5.0), unfreeze: str = "classifier"):
     """train_cifake_forensics.py:276-379: the CIFAKE tree's balanced sample and split, one feature extraction per
     split (two views of the training images with ``flip``; with ``jitter_views`` = K, K colour-jittered draws of
     each, from ``jitter_params(N, K, seed)``; with ``blur_views`` = K, K views blurred with probability ``blur_p``
@@ -487,7 +649,14 @@ def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epoch
     K views saved as JPEGs at a quality drawn from the closed range ``jpeg_quality`` and loaded back,
     ``jpeg_params(N, K, seed, jpeg_quality)`` -- the ones that are non-zero must be equal, and view v is jittered
     first, blurred next and compressed last, the order of the reference dataset's Compose), unreadable images
-    dropped and counted, then the trainer.  Returns the history."""
+    dropped and counted, then the trainer.  Returns the history.
+
+    ``unfreeze`` = "classifier": the linear probe on cached pooled rows (``ClassifierTrainer``).  "head": features.8
+    as well, on cached trunk rows (``HeadStageTrainer``; the rows stay on the device, 62,720 bytes per view and
+    image)."""
+    if unfreeze not in ("classifier", "head"):
+        raise ValueError(f"unfreeze must be 'classifier' or 'head', got {unfreeze!r}")
+    level = "trunk" if unfreeze == "head" else "pooled"
     jitter_views, blur_views, jpeg_views = int(jitter_views), int(blur_views), int(jpeg_views)
     if jitter_views < 0 or blur_views < 0 or jpeg_views < 0:
         raise ValueError(f"jitter_views, blur_views and jpeg_views must be >= 0, got {jitter_views}, {blur_views}, "
@@ -509,18 +678,28 @@ def train_cifake(cifake_root: str, batch_size: int = 16, lr: float = 1e-4, epoch
     jitter = jitter_params(len(tr_p), jitter_views, seed) if jitter_views else None
     jpeg = jpeg_params(len(tr_p), jpeg_views, seed, jpeg_quality) if jpeg_views else None
     blur = blur_params(len(tr_p), blur_views, seed, blur_p, blur_sigma) if blur_views else None
-    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter, jpeg=jpeg, blur=blur)
+    out = extract_image_features(forensics, tr_p, flip=flip, jitter=jitter, jpeg=jpeg, blur=blur, level=level)
     ok_t = out[-1]
-    xv, ok_v = extract_image_features(forensics, va_p)
+    xv, ok_v = extract_image_features(forensics, va_p, level=level)
     dropped = int((~ok_t).sum() + (~ok_v).sum())
     if dropped:
         print(f"Dropped {dropped} unreadable images")
     tr_y, va_y = np.asarray(tr_y)[ok_t], np.asarray(va_y)[ok_v]
-    train = (out[0][..., ok_t, :], out[1][..., ok_t, :]) if flip else out[0][..., ok_t, :]
-    trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip,
-                                jitter_views=views)
-    history = trainer.fit(train, tr_y, xv[ok_v], va_y, checkpoint_path=checkpoint_path,
-                          save_full_model=save_full_model)
+    if level == "trunk":
+        def readable(t, ok):  # device tensors [.., N, 49, 320]: nothing dropped (the usual case) makes no second copy
+            return t if ok.all() else t[..., torch.from_numpy(np.flatnonzero(ok)).to(t.device), :, :]
+        train = tuple(readable(o, ok_t) for o in out[:-1])
+        train = train if flip else train[0]
+        trainer = HeadStageTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip,
+                                   jitter_views=views)
+        history = trainer.fit(train, tr_y, readable(xv, ok_v), va_y, checkpoint_path=checkpoint_path,
+                              save_full_model=save_full_model)
+    else:
+        train = (out[0][..., ok_t, :], out[1][..., ok_t, :]) if flip else out[0][..., ok_t, :]
+        trainer = ClassifierTrainer(forensics, batch_size=batch_size, epochs=epochs, lr=lr, seed=seed, flip=flip,
+                                    jitter_views=views)
+        history = trainer.fit(train, tr_y, xv[ok_v], va_y, checkpoint_path=checkpoint_path,
+                              save_full_model=save_full_model)
     for h in history:
         print(f"Epoch {h['epoch']}/{epochs}  Train Loss: {h['train_loss']:.4f}, Train Acc: {h['train_acc']:.2f}%  "
               f"Val Loss: {h['val_loss']:.4f}, Val Acc: {h['val_acc']:.2f}%")
@@ -551,12 +730,15 @@ def main(argv=None) -> None:
                          "with --jitter-views the same K: jittered first, compressed after)")
     ap.add_argument("--jpeg-quality", type=int, nargs=2, default=(40, 80), metavar=("LO", "HI"),
                     help="the closed range the JPEG quality is drawn from")
+    ap.add_argument("--unfreeze", choices=("classifier", "head"), default="classifier",
+                    help="classifier: the linear probe on pooled rows; head: features.8 (1x1 conv + BatchNorm affine) "
+                         "as well, on cached trunk rows kept on the device (62,720 bytes per view and image)")
     ap.add_argument("--checkpoint", default=DEFAULT_FILE)
     a = ap.parse_args(argv)
     train_cifake(a.root, batch_size=a.batch_size, lr=a.lr, epochs=a.epochs, sample_per_label=a.samples_per_label,
                  checkpoint_path=a.checkpoint, flip=not a.no_flip, jitter_views=a.jitter_views, jpeg_views=a.jpeg_views,
                  jpeg_quality=tuple(a.jpeg_quality), blur_views=a.blur_views, blur_p=a.blur_p,
-                 blur_sigma=tuple(a.blur_sigma))
+                 blur_sigma=tuple(a.blur_sigma), unfreeze=a.unfreeze)
 
 
 if __name__ == "__main__":

@@ -820,6 +820,15 @@ int mmf_effnet_pooled(mmf_handle* h, const uint8_t* img, int B, float* pooled, v
   return run_effnet(h, img, nullptr, B, nullptr, nullptr, 1, (hipStream_t)stream, 0, pooled);
 }
 
+int mmf_effnet_trunk(mmf_handle* h, const uint8_t* img, int B, float* trunk, void* stream) {
+  if (!h || !img || !trunk) return fail(MMF_EINVAL, "null argument");
+  if (!(h->ready & RDY_EFFNET)) return fail(MMF_EINVAL, "EfficientNet not loaded");
+  if ((uintptr_t)trunk & 15) return fail(MMF_EINVAL, "effnet_trunk: trunk must be 16-byte aligned");
+  CHK(check_cap(h, B, 1, 1));
+  HIPCHK(hipSetDevice(h->device));
+  return run_effnet(h, img, nullptr, B, nullptr, nullptr, 1, (hipStream_t)stream, 0, nullptr, trunk);
+}
+
 int mmf_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, void* stream) {
   if (!src || !dst) return fail(MMF_EINVAL, "null argument");
   if (B < 1 || H < 1 || W < 1 || C < 1 || (double)B * H * W >= 549755813888.0 /* 2^39 pixels: the grid */)
@@ -901,6 +910,52 @@ int mmf_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, 
   if (R < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "effcls_eval: R=%d (>= 1) batch=%d (1..64)", R, batch);
   CHK(check_aligned("effcls_eval", 4, {feat, labels, params, batch_loss, row_logits}));
   HIPCHK(launch_effcls_eval(feat, labels, R, batch, params, batch_loss, row_logits, (hipStream_t)stream));
+  return 0;
+}
+
+static_assert(kEffHeadParams == MMF_EFFHEAD_PARAMS, "header and kernels");
+int64_t mmf_effhead_ws_bytes(int batch) { return (int64_t)effhead_ws_bytes(batch); }
+// the kernels use bn_eps as an fp32 value: that value, not the double, must be positive and finite
+static bool effhead_eps_ok(double bn_eps) {
+  const float e = (float)bn_eps;
+  return e > 0.0f && std::isfinite(e);
+}
+
+int mmf_effhead_train_epoch(const float* trunk, const int32_t* labels, int R, const int32_t* perm, int N,
+                            const uint64_t* keep, float p_drop, int batch, const float* bn_mean, const float* bn_var,
+                            double bn_eps, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int step0, float* params, float* exp_avg, float* exp_avg_sq, float* step_loss,
+                            int32_t* step_correct, float* grad_out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!trunk || !labels || !perm || !bn_mean || !bn_var || !params || !exp_avg || !exp_avg_sq || !step_loss ||
+      !step_correct || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  if (R < 1 || N < 1 || batch < 1 || batch > 64 || step0 < 0 || !(p_drop >= 0.f && p_drop < 1.f))
+    return fail(MMF_EINVAL, "effhead_train_epoch: R=%d N=%d (>= 1) batch=%d (1..64) step0=%d (>= 0) p_drop=%g ([0, 1))",
+                R, N, batch, step0, (double)p_drop);
+  if (!effhead_eps_ok(bn_eps))
+    return fail(MMF_EINVAL, "effhead_train_epoch: bn_eps=%g must be positive and finite as an fp32 value", bn_eps);
+  CHK(check_ws("effhead_train_epoch", ws_bytes, effhead_ws_bytes(batch)));
+  CHK(check_aligned("effhead_train_epoch", 4, {labels, perm, bn_mean, bn_var, step_loss, step_correct}));
+  CHK(check_aligned("effhead_train_epoch", 16, {trunk, params, exp_avg, exp_avg_sq, grad_out, ws}, true, keep));
+  HIPCHK(launch_effhead_train_epoch(trunk, labels, R, perm, N, keep, p_drop, batch, bn_mean, bn_var, bn_eps, lr, beta1,
+                                    beta2, eps, weight_decay, step0, params, exp_avg, exp_avg_sq, step_loss,
+                                    step_correct, grad_out, (float*)ws, (hipStream_t)stream));
+  return 0;
+}
+
+int mmf_effhead_eval(const float* trunk, const int32_t* labels, int R, int batch, const float* params,
+                     const float* bn_mean, const float* bn_var, double bn_eps, float* batch_loss, float* row_logits,
+                     void* ws, int64_t ws_bytes, void* stream) {
+  if (!trunk || !labels || !params || !bn_mean || !bn_var || !batch_loss || !row_logits || !ws)
+    return fail(MMF_EINVAL, "null argument");
+  if (R < 1 || batch < 1 || batch > 64) return fail(MMF_EINVAL, "effhead_eval: R=%d (>= 1) batch=%d (1..64)", R, batch);
+  if (!effhead_eps_ok(bn_eps))
+    return fail(MMF_EINVAL, "effhead_eval: bn_eps=%g must be positive and finite as an fp32 value", bn_eps);
+  CHK(check_ws("effhead_eval", ws_bytes, effhead_ws_bytes(batch)));
+  CHK(check_aligned("effhead_eval", 4, {labels, bn_mean, bn_var, batch_loss, row_logits}));
+  CHK(check_aligned("effhead_eval", 16, {trunk, params, ws}));
+  HIPCHK(launch_effhead_eval(trunk, labels, R, batch, params, bn_mean, bn_var, bn_eps, batch_loss, row_logits,
+                             (float*)ws, (hipStream_t)stream));
   return 0;
 }
 

@@ -898,7 +898,25 @@ __global__ __launch_bounds__(256) void gap_pooled_kernel(const f16_t* x, int HW,
   }
 }
 
+// The last MBConv block's output as fp32 rows (mmf_effnet_trunk): every fp16 value converted exactly; one thread per
+// 8 elements (n8 groups of 8)
+__global__ __launch_bounds__(256) void f16_rows_to_f32_kernel(const f16_t* x, float* out, size_t n8) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const uint4 v = *reinterpret_cast<const uint4*>(x + i * 8);
+  float* o = out + i * 8;
+  *reinterpret_cast<float4*>(o) = make_float4(lo_h(v.x), hi_h(v.x), lo_h(v.y), hi_h(v.y));
+  *reinterpret_cast<float4*>(o + 4) = make_float4(lo_h(v.z), hi_h(v.z), lo_h(v.w), hi_h(v.w));
+}
+
 }  // namespace
+
+hipError_t launch_f16_rows_to_f32(const f16_t* x, float* out, size_t n, hipStream_t s) {
+  if (n == 0 || (n % 8)) return hipErrorInvalidValue;
+  const size_t n8 = n / 8;
+  hipLaunchKernelGGL(f16_rows_to_f32_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, x, out, n8);
+  return hipGetLastError();
+}
 
 #ifdef MMF_EFF_STAMP
 // diagnostic build: where the stamping kernels write (nullptr = off)

@@ -54,7 +54,7 @@ EffWs<T> eff_ws(const Workspace& w, T* a, T* b, T* exp, T* dw, int b0) {
 // The fp32 tower (option effnet_fp32): same network, same folded weights (fp32 copies of the 1x1
 // convs), activations fp32 throughout -- no fusion, one launch per layer.
 int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score,
-                 int score_stride, hipStream_t s, int img0, float* pooled) {
+                 int score_stride, hipStream_t s, int img0, float* pooled, float* trunk) {
   if (h->ws.e32_cap_b < img0 + B) return fail(MMF_EINVAL, "effnet_fp32: fp32 tower workspaces not reserved");
   const EffWs<float> w = eff_ws(h->ws, h->ws.e32_a, h->ws.e32_b, h->ws.e32_exp, h->ws.e32_dw, img0);
   float* cur = w.e_a;
@@ -95,6 +95,10 @@ int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, fl
     H = Ho;
     W = Wo;
   }
+  if (trunk) {  // mmf_effnet_trunk: the last block's output, copied; no head GEMM, pool or classifier
+    HIPCHK(hipMemcpyAsync(trunk, cur, sizeof(float) * (size_t)B * H * W * 320, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
   {
     ProfScope ps(h, s, PK_PW32, 2.0 * B * H * W * 320 * 1280, 4.0 * B * H * W * (320 + 1280));
     HIPCHK(launch_pw32(cur, h->e_head.w32, h->e_head.b, nullptr, 1, nullptr, w.e_exp, B * H * W, 1280, 320, 3, s,
@@ -109,8 +113,8 @@ int run_effnet32(mmf_handle* h, const uint8_t* img, const float* xf32, int B, fl
 }  // namespace
 
 int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score, int score_stride,
-               hipStream_t s, int img0, float* pooled) {
-  if (h->opt.effnet_fp32) return run_effnet32(h, img, xf32, B, logits, score, score_stride, s, img0, pooled);
+               hipStream_t s, int img0, float* pooled, float* trunk) {
+  if (h->opt.effnet_fp32) return run_effnet32(h, img, xf32, B, logits, score, score_stride, s, img0, pooled, trunk);
   const EffWs<f16_t> w = eff_ws(h->ws, h->ws.e_a, h->ws.e_b, h->ws.e_exp, h->ws.e_dw, img0);
   f16_t* cur = w.e_a;
   f16_t* nxt = w.e_b;
@@ -163,6 +167,10 @@ int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, floa
     std::swap(cur, nxt);
     H = Ho;
     W = Wo;
+  }
+  if (trunk) {  // mmf_effnet_trunk: the last block's output, every fp16 value converted exactly
+    HIPCHK(launch_f16_rows_to_f32(cur, trunk, (size_t)B * H * W * 320, s));
+    return 0;
   }
   GemmArgs g = gemm_args(cur, 320, h->e_head, B * H * W);
   g.act = 3;

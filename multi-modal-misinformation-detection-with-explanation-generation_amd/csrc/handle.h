@@ -488,9 +488,10 @@ int run_clip_image_pooled(mmf_handle* h, const uint8_t* img, int B, float* poole
 int run_clip_text_pooled(mmf_handle* h, const int32_t* ids, const int32_t* mask, int B, int L, float* pooled,
                          hipStream_t s);
 // a chunk starting at image img0 works in its own slice of every workspace (mmf_effnet_forward); pooled
-// (mmf_effnet_pooled): the classifier's input rows fp32 [B][1280] instead of the classifier
+// (mmf_effnet_pooled): the classifier's input rows fp32 [B][1280] instead of the classifier; trunk
+// (mmf_effnet_trunk): the last MBConv block's output fp32 [B][49][320], and nothing after it
 int run_effnet(mmf_handle* h, const uint8_t* img, const float* xf32, int B, float* logits, float* score, int score_stride,
-               hipStream_t s, int img0 = 0, float* pooled = nullptr);
+               hipStream_t s, int img0 = 0, float* pooled = nullptr, float* trunk = nullptr);
 
 // EfficientNet-B0: the geometry of block j of stage si (no weights), and the activation elements per
 // image it implies: block input/output, expanded, depthwise output, SE pool partials (nchunks x

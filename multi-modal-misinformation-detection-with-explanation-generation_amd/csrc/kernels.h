@@ -218,6 +218,22 @@ hipError_t launch_effcls_train_epoch(const float* feat, const int32_t* labels, i
                                      float* grad_out, hipStream_t s);
 hipError_t launch_effcls_eval(const float* feat, const int32_t* labels, int R, int batch, const float* params,
                               float* batch_loss, float* row_logits, hipStream_t s);
+// EfficientNet's head conv stage (features.8: 1x1 conv, eval-mode BatchNorm, SiLU) trained with the classifier on
+// cached trunk rows [R][49][320] (effhead_train.hip; include/mmf_hip.h mmf_effhead_train_epoch / mmf_effhead_eval):
+// three launches per optimizer step (forward, classifier step, owner-per-tile backward with Adam in the epilogue), two
+// per eval batch; ws holds effhead_ws_bytes(batch) bytes (0 for a batch outside 1..64); hipErrorInvalidValue on a bad
+// R / N / batch / p_drop with nothing launched
+constexpr int kEffHeadParams = 414722;  // W [1280][320] | gamma [1280] | beta [1280] | Wc [2][1280] | bc [2]
+size_t effhead_ws_bytes(int batch);
+hipError_t launch_effhead_train_epoch(const float* trunk, const int32_t* labels, int R, const int32_t* perm, int N,
+                                      const uint64_t* keep, float p_drop, int batch, const float* bn_mean,
+                                      const float* bn_var, double bn_eps, double lr, double beta1, double beta2,
+                                      double eps, double weight_decay, int step0, float* params, float* exp_avg,
+                                      float* exp_avg_sq, float* step_loss, int32_t* step_correct, float* grad_out,
+                                      float* ws, hipStream_t s);
+hipError_t launch_effhead_eval(const float* trunk, const int32_t* labels, int R, int batch, const float* params,
+                               const float* bn_mean, const float* bn_var, double bn_eps, float* batch_loss,
+                               float* row_logits, float* ws, hipStream_t s);
 // dst[b][y][x][c] = src[b][y][W - 1 - x][c] (uint8; mmf_hflip_u8)
 hipError_t launch_hflip_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, hipStream_t s);
 // ColorJitter on uint8 [B][H][W][3], byte-exact with torchvision's PIL backend (jitter.hip; include/mmf_hip.h
@@ -331,6 +347,8 @@ hipError_t launch_gap_classifier(const f16_t* x, int HW, int C, const float* w, 
                                  float* score, int score_stride, int B, hipStream_t s);
 // the classifier's input row alone (mmf_effnet_pooled): pooled fp32 [B][C] = the ascending-pixel sum * (1 / HW)
 hipError_t launch_gap_pooled(const f16_t* x, int HW, int C, float* pooled, int B, hipStream_t s);
+// n fp16 values (a multiple of 8, both pointers 16-byte aligned) converted exactly to fp32 (mmf_effnet_trunk)
+hipError_t launch_f16_rows_to_f32(const f16_t* x, float* out, size_t n, hipStream_t s);
 hipError_t launch_fill_strided(float* p, int stride, int B, float v, hipStream_t s);
 // fused MBConv front: expand 1x1 (we fp16 [C][cin], be fp32, BN folded) + SiLU computed per input
 // tile into LDS, then the depthwise conv of launch_dwconv (same outputs, same pool partials)

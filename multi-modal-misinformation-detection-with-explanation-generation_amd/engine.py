@@ -278,6 +278,19 @@ class Engine:
             return pooled
         return precision.rerun_if(self.effnet_overflow, run, lambda p: (p * 0).sum(1).cpu().numpy())  # 0 or NaN per row
 
+    def effnet_trunk(self, img):
+        """What the head conv stage reads (mmf_effnet_trunk): the last MBConv block's output, float32 [B, 49, 320] on
+        the device (positions row-major over 7 x 7, channels innermost), by effnet_forward's launch sequence for the
+        tower in use without the head GEMM, the pool and the classifier.  The same run-time trap as effnet_pooled."""
+        img = self._u8(img)
+        B = img.shape[0]
+        trunk = self._f32(B, 49, 320)
+
+        def run():
+            check(self.lib.mmf_effnet_trunk(self.h, ptr(img), B, ptr(trunk), stream_ptr()), "mmf_effnet_trunk")
+            return trunk
+        return precision.rerun_if(self.effnet_overflow, run, lambda t: (t * 0).sum((1, 2)).cpu().numpy())
+
     def hflip(self, img):
         """A staged uint8 [B, H, W, C] window mirrored left-right (mmf_hflip_u8) into a new device tensor."""
         t = self._tensor(img)
@@ -665,6 +678,52 @@ class Engine:
         batch_loss, row_logits = self._f32(nb), self._f32(R, 2)
         check(self.lib.mmf_effcls_eval(ptr(feat), ptr(labels), R, int(batch), ptr(params), ptr(batch_loss),
                                        ptr(row_logits), stream_ptr()), "mmf_effcls_eval")
+        return batch_loss, row_logits
+
+    EFFHEAD_PARAMS = 414722  # MMF_EFFHEAD_PARAMS: features.8.0.weight | 8.1.weight | 8.1.bias | classifier.1.weight | .bias
+    TRUNK_ROW = 49 * 320     # floats of one image's trunk rows
+
+    def effhead_train_epoch(self, trunk, labels, perm, keep, p_drop: float, batch: int, bn_mean, bn_var, bn_eps: float,
+                            lr: float, betas, eps: float, weight_decay: float, step0: int, params, exp_avg,
+                            exp_avg_sq, grad_out=None):
+        """One epoch of head-stage training (mmf_effhead_train_epoch): device tensors trunk float32 [R, 49, 320] and
+        labels int32 [R] (the row bank), perm int32 [N] (bank rows), keep int64 [N, 20] (the uint64 masks' bits, on the
+        pooled row) or None; bn_mean / bn_var float32 [1280], read only; params / exp_avg / exp_avg_sq float32
+        [414722], updated in place.  Returns (step_loss float32 [nsteps], step_correct int32 [nsteps]) on the device;
+        nothing is synchronised."""
+        R, N, P = int(labels.shape[0]), int(perm.shape[0]), self.EFFHEAD_PARAMS
+        self._check_tensors("effhead_train_epoch", (
+            ("trunk", trunk, torch.float32, self.TRUNK_ROW * R, False), ("labels", labels, torch.int32, R, False),
+            ("perm", perm, torch.int32, N, False), ("keep", keep, torch.int64, 20 * N, True),
+            ("bn_mean", bn_mean, torch.float32, 1280, False), ("bn_var", bn_var, torch.float32, 1280, False),
+            ("params", params, torch.float32, P, False), ("exp_avg", exp_avg, torch.float32, P, False),
+            ("exp_avg_sq", exp_avg_sq, torch.float32, P, False), ("grad_out", grad_out, torch.float32, P, True)))
+        nsteps = self._nsteps(N, batch)
+        step_loss = self._f32(nsteps)
+        step_correct = torch.empty(nsteps, dtype=torch.int32, device=self.device)
+        ws = self._workspace("effhead_train", self.lib.mmf_effhead_ws_bytes(int(batch)))
+        check(self.lib.mmf_effhead_train_epoch(ptr(trunk), ptr(labels), R, ptr(perm), N, ptr(keep), float(p_drop),
+                                               int(batch), ptr(bn_mean), ptr(bn_var), float(bn_eps), float(lr),
+                                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                               int(step0), ptr(params), ptr(exp_avg), ptr(exp_avg_sq), ptr(step_loss),
+                                               ptr(step_correct), ptr(grad_out), ptr(ws), ws.numel(), stream_ptr()),
+              "mmf_effhead_train_epoch")
+        return step_loss, step_correct
+
+    def effhead_eval(self, trunk, labels, batch: int, params, bn_mean, bn_var, bn_eps: float):
+        """validate's forward on cached trunk rows (mmf_effhead_eval): consecutive batches in row order ->
+        (batch_loss float32 [nbatches], row_logits float32 [R, 2]) on the device."""
+        R = int(labels.shape[0])
+        self._check_tensors("effhead_eval", (
+            ("trunk", trunk, torch.float32, self.TRUNK_ROW * R, False), ("labels", labels, torch.int32, R, False),
+            ("bn_mean", bn_mean, torch.float32, 1280, False), ("bn_var", bn_var, torch.float32, 1280, False),
+            ("params", params, torch.float32, self.EFFHEAD_PARAMS, False)))
+        nb = self._nsteps(R, batch)
+        batch_loss, row_logits = self._f32(nb), self._f32(R, 2)
+        ws = self._workspace("effhead_train", self.lib.mmf_effhead_ws_bytes(int(batch)))
+        check(self.lib.mmf_effhead_eval(ptr(trunk), ptr(labels), R, int(batch), ptr(params), ptr(bn_mean), ptr(bn_var),
+                                        float(bn_eps), ptr(batch_loss), ptr(row_logits), ptr(ws), ws.numel(),
+                                        stream_ptr()), "mmf_effhead_eval")
         return batch_loss, row_logits
 
     def vault_topk(self, q_unit: torch.Tensor, k: int = 5, thresh: float = 0.85, text_emb=None):

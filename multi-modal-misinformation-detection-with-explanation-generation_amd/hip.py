@@ -41,6 +41,11 @@ SIGNATURES = {
     "mmf_jpeg_roundtrip_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "mmf_effcls_train_epoch": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmf_effcls_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "mmf_effnet_trunk": (_I, [_P, _P, _I, _P, _P]),
+    "mmf_effhead_ws_bytes": (ctypes.c_int64, [_I]),
+    "mmf_effhead_train_epoch": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _P, _P, _D, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P,
+                                     _P, _P, _P, ctypes.c_int64, _P]),
+    "mmf_effhead_eval": (_I, [_P, _P, _I, _I, _P, _P, _P, _D, _P, _P, _P, ctypes.c_int64, _P]),
     "mmf_clip_image": (_I, [_P, _P, _I, _P, _P]),
     "mmf_clip_text": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "mmf_clip_consistency": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
