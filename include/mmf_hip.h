@@ -922,6 +922,24 @@ int mmf_vault_sort_cand_f32(const float* cs, const int32_t* cidx, int chunks, in
 int mmf_jpeg_block_roundtrip_raw(const int16_t* blocks, const uint8_t* table, int n, int16_t* coefs, uint8_t* samples,
                                  int32_t* outside, void* stream);
 
+/* Test-only: mmf_resize_pil's plan for one width x height image (csrc/resize_host.cpp; host only, no handle, no
+ * device call).  geom 0 = the EfficientNet squash (bilinear), 1 = CLIP's shortest edge -> 224 (bicubic) + centre
+ * crop.  out12 int32 [12] (host) = ow, oh (Pillow's resize output size), cx, cy (the window's offset in it),
+ * need_h, need_v (the pass runs: the size changes on that axis), y0, y1 (the source rows the horizontal pass
+ * writes for the window's vertical taps), ksh, ksv (taps per coordinate; 1 for a pass that does not run), x0, x1
+ * (0, 0, except where Image.resize runs the vertical pass first -- both passes run, height > 100 * width and the
+ * height shrinks: then the source columns the vertical pass writes for the window's horizontal taps).
+ * MMF_ERANGE: a pass needs more than 96 taps; MMF_EINVAL: a non-positive size, another geom, a NULL pointer.
+ * mmf_resize_supported is 1 exactly where both geometries plan. */
+int mmf_resize_plan(int width, int height, int geom, int32_t* out12);
+
+/* Test-only: the coefficient kernel of mmf_resize_pil on that plan's one job (device pointers).  coef int32
+ * [224 * ksh + 224 * ksv]: the 22-bit fixed-point weights of the 224 window coordinates, horizontal then vertical,
+ * taps at and past a coordinate's n zero; bounds int32 [2][224][2]: (xmin, n) per axis (0 horizontal, 1 vertical)
+ * and window coordinate.  An axis whose pass does not run has ks = 1 and values no pass reads.  Synchronous.
+ * The same error codes, with nothing launched. */
+int mmf_resize_coef_raw(int width, int height, int geom, int32_t* coef, int32_t* bounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,10 +375,16 @@ struct ResizeJob {
   int need_h, need_v; // Pillow runs the pass (size changes on that axis)
   int y0, y1;         // source rows the window's vertical taps read
   int ksh, ksv;       // taps per coordinate, horizontal / vertical
-  long long tmp_off;  // byte offset of this job's [y1 - y0][224][3] horizontal-pass rows
+  long long tmp_off;  // byte offset of this job's [y1 - y0][224][3] first-pass rows
   int coef_off;       // int32 offset of [224][ksh] then [224][ksv] coefficients
   int ps;             // source bytes per pixel: 3 (RGB) or 4 (RGBX, Pillow's in-memory layout)
+  int x0, x1;         // x1 > 0: the vertical pass runs first (Image.resize's order for a source over 100 times as
+                      // tall as wide whose height shrinks), over the source columns the window's horizontal taps
+                      // read; tmp is then [x1 - x0][224][3]
 };
+// the coefficient launch of launch_resize_pil alone: coef int32 [sum 224 * (ksh + ksv)] at each job's coef_off,
+// bounds int32 [njobs][2][224][2] = (xmin, n) per job, axis (0 horizontal, 1 vertical) and window coordinate
+hipError_t launch_resize_coef(const ResizeJob* jobs, int njobs, int32_t* coef, int32_t* bounds, hipStream_t s);
 hipError_t launch_resize_pil(const uint8_t* src, const ResizeJob* jobs, int njobs, int max_rows, int32_t* coef,
                              int32_t* bounds, uint8_t* tmp, uint8_t* const* outs, hipStream_t s);
 

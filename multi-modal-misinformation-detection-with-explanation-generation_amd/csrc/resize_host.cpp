@@ -60,8 +60,20 @@ bool plan_job(int w, int h, int geom, ResizeJob* J) {
     J->y0 = J->cy;
     J->y1 = J->cy + 224;
   }
+  // Image.resize (Pillow's Image.py) resamples a source more than 100 times as tall as wide whose height shrinks
+  // vertically first, to (w, oh), and horizontally after; with one pass alone the order is moot
+  if (J->need_h && J->need_v && (long long)h > (long long)w * 100 && J->oh < h) {
+    const AxisPlan a = axis_plan(w, J->ow, J->filt);
+    int lo, hi;
+    tap_range(a, w, J->cx, &lo, &hi);
+    J->x0 = lo;
+    tap_range(a, w, J->cx + 223, &lo, &hi);
+    J->x1 = hi;
+  }
   return true;
 }
+// lines of the first pass: source rows, or source columns where the vertical pass runs first
+int first_pass_lines(const ResizeJob& J) { return J.x1 > 0 ? J.x1 - J.x0 : J.y1 - J.y0; }
 }  // namespace
 
 extern "C" {
@@ -89,9 +101,9 @@ int mmf_resize_pil(mmf_handle* h, const uint8_t* src, const int64_t* offsets, co
       J.ps = pixel_bytes;
       J.tmp_off = tmp;
       J.coef_off = coef;
-      tmp += (long long)(J.y1 - J.y0) * 224 * 3;
+      tmp += (long long)first_pass_lines(J) * 224 * 3;
       coef += 224 * (J.ksh + J.ksv);
-      max_rows = std::max(max_rows, J.y1 - J.y0);
+      max_rows = std::max(max_rows, first_pass_lines(J));
       jobs.push_back(J);
       outs.push_back(o + (size_t)i * 224 * 224 * 3);
     }
@@ -118,9 +130,42 @@ int mmf_resize_pil(mmf_handle* h, const uint8_t* src, const int64_t* offsets, co
 }
 
 int mmf_resize_supported(int width, int height) {
-  if (width <= 0 || height <= 0) return 0;
+  int32_t p[12];
+  return mmf_resize_plan(width, height, 0, p) == 0 && mmf_resize_plan(width, height, 1, p) == 0 ? 1 : 0;
+}
+
+// Test-only: plan_job's geometry for one image (tests/test_resize_refs_cpu.py)
+int mmf_resize_plan(int width, int height, int geom, int32_t* out12) {
+  if (!out12) return fail(MMF_EINVAL, "null argument");
+  if (width <= 0 || height <= 0) return fail(MMF_EINVAL, "resize_plan: size %dx%d", width, height);
+  if (geom != 0 && geom != 1) return fail(MMF_EINVAL, "resize_plan: geom %d (0 EfficientNet, 1 CLIP)", geom);
   ResizeJob J;
-  return plan_job(width, height, 0, &J) && plan_job(width, height, 1, &J) ? 1 : 0;
+  if (!plan_job(width, height, geom, &J))
+    return fail(MMF_ERANGE, "resize_plan: %dx%d: downscale beyond %d taps per output pixel", width, height, kResizeKMax);
+  const int32_t v[12] = {J.ow, J.oh, J.cx, J.cy, J.need_h, J.need_v, J.y0, J.y1, J.ksh, J.ksv, J.x0, J.x1};
+  std::copy(v, v + 12, out12);
+  return 0;
+}
+
+// Test-only: the coefficient kernel of mmf_resize_pil on the one job of a width x height image
+// (tests/test_gpu_resize.py).  Synchronous: the job table is a temporary of this call
+int mmf_resize_coef_raw(int width, int height, int geom, int32_t* coef, int32_t* bounds, void* stream) {
+  if (!coef || !bounds) return fail(MMF_EINVAL, "null argument");
+  if (width <= 0 || height <= 0) return fail(MMF_EINVAL, "resize_coef: size %dx%d", width, height);
+  if (geom != 0 && geom != 1) return fail(MMF_EINVAL, "resize_coef: geom %d (0 EfficientNet, 1 CLIP)", geom);
+  ResizeJob J;
+  if (!plan_job(width, height, geom, &J))
+    return fail(MMF_ERANGE, "resize_coef: %dx%d: downscale beyond %d taps per output pixel", width, height, kResizeKMax);
+  hipStream_t s = (hipStream_t)stream;
+  ResizeJob* dj = nullptr;
+  HIPCHK(hipMalloc((void**)&dj, sizeof(ResizeJob)));
+  hipError_t e = hipMemcpyAsync(dj, &J, sizeof(ResizeJob), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_resize_coef(dj, 1, coef, bounds, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)hipFree(dj);
+  if (e != hipSuccess || e2 != hipSuccess)
+    return fail(MMF_EIO, "resize_coef: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  return 0;
 }
 
 }  // extern "C"

@@ -169,7 +169,11 @@ class Engine:
         centre-crop windows, bit-exact with Pillow (mmf_resize_pil).  The images cross PCIe once,
         packed (threaded copies) into a pinned staging buffer."""
         arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        ps = arrs[0].shape[2] if arrs else 3
+        if not arrs:  # nothing to resample: empty outputs, no device call
+            empty = [torch.empty((0, 224, 224, 3), dtype=torch.uint8, device=self.device) if k else None
+                     for k in (effnet, clip)]
+            return empty[0], empty[1]
+        ps = arrs[0].shape[2]
         for a in arrs:
             if not (a.ndim == 3 and a.shape[2] == ps and ps in (3, 4)):
                 raise ValueError(f"expected HxWx{ps} uint8, got {a.shape}")

@@ -143,6 +143,9 @@ SIGNATURES = {
     "mmf_vault_topk_f32": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P]),
     "mmf_vault_sort_cand_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
     "mmf_jpeg_block_roundtrip_raw": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    # mmf_resize_pil's plan and coefficient kernel for one image (csrc/resize_host.cpp)
+    "mmf_resize_plan": (_I, [_I, _I, _I, _P]),
+    "mmf_resize_coef_raw": (_I, [_I, _I, _I, _P, _P, _P]),
 }
 
 JITTER_CHUNKS = 256  # MMF_JITTER_CHUNKS: mmf_color_jitter_u8's ws is uint64 [B][JITTER_CHUNKS]

@@ -60,8 +60,25 @@ def _clip8(acc):
     return np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
 
 
+def vertical_first(w: int, h: int, out_h: int) -> bool:
+    """Image.resize's order of the passes (Image.py): a source more than 100 times as tall as wide whose height
+    shrinks is resampled vertically first -- to (w, out_h) -- and horizontally after; every other in one
+    ImagingResample call, horizontally first.  The intermediate rounds to uint8, so the order shows in the bytes."""
+    return h > w * 100 and out_h < h
+
+
 def resize(img: np.ndarray, out_w: int, out_h: int, name: str) -> np.ndarray:
     """Image.resize((out_w, out_h), BILINEAR | BICUBIC) of a uint8 HxWxC array."""
+    h, w, c = img.shape
+    if (out_w, out_h) == (w, h):
+        return img.copy()
+    if vertical_first(w, h, out_h):
+        return _resample(_resample(img, w, out_h, name), out_w, out_h, name)
+    return _resample(img, out_w, out_h, name)
+
+
+def _resample(img: np.ndarray, out_w: int, out_h: int, name: str) -> np.ndarray:
+    """ImagingResample: the horizontal pass over the rows the vertical pass reads, then the vertical pass."""
     h, w, c = img.shape
     if (out_w, out_h) == (w, h):
         return img.copy()
